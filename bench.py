@@ -26,6 +26,11 @@ link carries a share in both directions; a gather of every step to rank 0 would 
 capped by rank 0's inbound links), issued on its own stream once those steps' results
 exist (sbr_batch_wait) so that it overlaps the later steps' sweeps.  value = all ranks'
 equilibria × steps / max-over-ranks time.
+
+A plain run sets up, warms up, times the steps, writes the last timed step's results when
+--dump-outputs DIR is given, and prints the result line.  --full adds what the headline figure
+does not need: the cpu_baseline leg (the CPU oracle on a sample of the workload) and the check of
+the last timed grid against the oracle, bit for bit.
 """
 from __future__ import annotations
 
@@ -262,7 +267,63 @@ def parse():
     ap.add_argument("--social-max-iter", type=int, default=500)
     ap.add_argument("--social-prof", action="store_true", help="social: per-phase cycle breakdown (diagnostic)")
     ap.add_argument("--social-dump", default="", help="social: save per-point status/fp_iters/rk_steps (.npz)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write the last timed step's result arrays as DIR/<name>.npy "
+                         "(float64, finite: NaN / inf are 0 there and coded in <name>_nonfinite.npy; a fixed seeded "
+                         "sample of the points when the whole grid would pass 64 MB)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the cpu_baseline leg and the check of the "
+                         "last timed grid against the oracle (each still switched off by --no-cpu-baseline / "
+                         "--no-verify), config2's phase breakdown, dropin's raw-call and Fig 5 loops")
+    a = ap.parse_args()
+    if not a.full:  # a plain run: set up, warm up, time the steps, dump, print
+        a.no_cpu_baseline = a.no_verify = True
+    return a
+
+
+MAX_BATCH = 256  # grids per batch call of the timed region (51 GB of results at 2048²)
+DUMP_BUDGET = 48 << 20  # bytes of one --dump-outputs over all its files (the limit is 64 MB)
+DUMP_SEED = 20240531
+
+
+def dump_outputs(dirname: str, fields: dict, world: int = 1, rank: int = 0) -> None:
+    """--dump-outputs: the per-point result arrays of the last timed step (torch tensors or numpy
+    arrays, one flat array of the same length per field) as float64 .npy files; integer fields are
+    widened (status through its unsigned view), so every value is exact.  Every file holds finite
+    numbers only: the NaN of a point without a run (ξ, AW_max) and an infinite tol are results,
+    so a float field is written as its values with 0 in those places and, beside it, as
+    <name>_nonfinite.npy (float32: 0 finite, 1 NaN, 2 +inf, 3 -inf), from which the caller's array
+    is rebuilt exactly.  When the arrays would pass the budget the same seeded sample of point
+    indices is taken from every field and saved beside them as sample_index.npy.  N ranks: every
+    rank writes its own shard as <name>.rank<r>.npy and the budget is split between them."""
+    d = Path(dirname)
+    d.mkdir(parents=True, exist_ok=True)
+    first = next(iter(fields.values()))
+    n = int(first.numel() if torch.is_tensor(first) else np.asarray(first).size)
+    n_float = sum(v.is_floating_point() if torch.is_tensor(v) else np.asarray(v).dtype.kind == "f"
+                  for v in fields.values())
+    keep = DUMP_BUDGET // world // (8 * (len(fields) + 1) + 4 * n_float)
+    idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n, keep, replace=False)) if n > keep else None
+    suffix = ".npy" if world == 1 else f".rank{rank}.npy"
+    for k, v in fields.items():
+        if torch.is_tensor(v):
+            v = v.reshape(-1)
+            if idx is not None:
+                v = v[torch.as_tensor(idx, device=v.device)]
+            v = v.cpu().numpy()
+        else:
+            v = np.asarray(v).reshape(-1)
+            if idx is not None:
+                v = v[idx]
+        if k == "status":
+            v = np.ascontiguousarray(v).view(np.uint32)
+        if v.dtype.kind == "f":
+            code = np.where(np.isnan(v), 1, np.where(v == np.inf, 2, np.where(v == -np.inf, 3, 0)))
+            np.save(d / (k + "_nonfinite" + suffix), code.astype(np.float32))
+            v = np.where(code == 0, v, 0.0)
+        np.save(d / (k + suffix), v.astype(np.float64))
+    if idx is not None:
+        np.save(d / ("sample_index" + suffix), idx.astype(np.float64))
 
 
 def main_small(a):
@@ -327,15 +388,19 @@ def main_small(a):
             r = eng.sweep_baseline(g, early_exit=5, out=host_out)
         dt = (time.perf_counter() - t0) / a.steps
         run = int(((r["status"] & sbr.STATUS["SBR_RUN"]) > 0).sum())
-        # phase breakdown of one more call (events on the call's stream + host clock)
-        eng.timing_enable(True)
-        tp = time.perf_counter()
-        eng.sweep_baseline(g, early_exit=5, out=host_out)
-        py_call = (time.perf_counter() - tp) * 1e3
-        phases = eng.host_phases()
-        eng.timing_read(None)
-        eng.timing_enable(False)
-        phases["python_call"] = py_call
+        if a.dump_outputs:
+            dump_outputs(a.dump_outputs, host_out)
+        phases = None
+        if a.full:
+            # phase breakdown of one more call (events on the call's stream + host clock)
+            eng.timing_enable(True)
+            tp = time.perf_counter()
+            eng.sweep_baseline(g, early_exit=5, out=host_out)
+            py_call = (time.perf_counter() - tp) * 1e3
+            phases = eng.host_phases()
+            eng.timing_read(None)
+            eng.timing_enable(False)
+            phases["python_call"] = py_call
         res = {"metric": "equilibria solved/sec on β×u grid (FP64), Fig 5 500x500, one host-API call per grid",
                "value": npts / dt, "unit": "equilibria/s", "n_gpus": 1, "steps": a.steps, "warmup": a.warmup,
                "ms_per_step": dt * 1e3, "higher_is_better": True, "scaling": None, "vs_baseline": None,
@@ -376,6 +441,8 @@ def main_multihost(a):
         eng.sweep_baseline(g, out=host_out)
         phases.append(eng.host_phases())
     dt = (time.perf_counter() - t0) / a.steps
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, host_out)
     mean = {k: float(np.mean([p[k] for p in phases])) for k in phases[0]}
     d2h_gbs = npts * 48 / n_dev / (mean["slowest_rank_d2h_pinned"] * 1e-3) / 1e9
     res = {"metric": "equilibria solved/sec on β×u grid (FP64), host-pointer n-device call (PCIe included)",
@@ -430,6 +497,18 @@ def main_dropin(a, eng, O):
         aw4, calls4 = _unchanged_loop(lr, m, u4)
     dt4 = (time.perf_counter() - t0) / reps
     n_run4 = int(np.isfinite(aw4).sum())
+    res = {"metric": "unchanged-script drop-in latency: solve_equilibrium_baseline(lr, econ) + get_AW_functions! "
+                     "per call (Fig 4 loop, host API)",
+           "value": dt4 / calls4 * 1e6, "unit": "us per call", "n_gpus": 1, "steps": reps, "warmup": 1,
+           "ms_per_step": dt4 * 1e3, "higher_is_better": False, "scaling": None, "vs_baseline": None,
+           "dtype": "f64", "data": "the reference's Fig 4 / Fig 5 grids (deterministic)",
+           "config": {"workload": "scripts/1_baseline.jl Fig 4 loop (5000 u, 5-NaN early exit) through the Python "
+                                  "mirror on one LearningResults (sbr_equilibrium_on_knots)"},
+           "fig4": {"calls": calls4, "run_points": n_run4, "seconds": dt4},
+           "libsbr_sha16": lib_sha()}
+    if not a.full:
+        print(json.dumps(res), flush=True)
+        return
     cdf = lr.learning_cdf
     k = 2000
     t1 = time.perf_counter()
@@ -450,18 +529,9 @@ def main_dropin(a, eng, O):
         calls5 += c
         run5 += int(np.isfinite(col).sum())
     dt5 = time.perf_counter() - t2
-    res = {"metric": "unchanged-script drop-in latency: solve_equilibrium_baseline(lr, econ) + get_AW_functions! "
-                     "per call (Fig 4 loop, host API)",
-           "value": dt4 / calls4 * 1e6, "unit": "us per call", "n_gpus": 1, "steps": reps, "warmup": 1,
-           "ms_per_step": dt4 * 1e3, "higher_is_better": False, "scaling": None, "vs_baseline": None,
-           "dtype": "f64", "data": "the reference's Fig 4 / Fig 5 grids (deterministic)",
-           "config": {"workload": "scripts/1_baseline.jl Fig 4 loop (5000 u, 5-NaN early exit) through the Python "
-                                  "mirror on one LearningResults (sbr_equilibrium_on_knots)"},
-           "fig4": {"calls": calls4, "run_points": n_run4, "seconds": dt4},
-           "raw_capi_us_per_call": raw * 1e6,
-           "fig5_500_unchanged": {"seconds": dt5, "solve_learning_seconds": learn5, "calls": calls5,
-                                  "run_points": run5, "us_per_call": (dt5 - learn5) / max(calls5, 1) * 1e6},
-           "libsbr_sha16": lib_sha()}
+    res.update(raw_capi_us_per_call=raw * 1e6,
+               fig5_500_unchanged={"seconds": dt5, "solve_learning_seconds": learn5, "calls": calls5,
+                                   "run_points": run5, "us_per_call": (dt5 - learn5) / max(calls5, 1) * 1e6})
     t3 = time.perf_counter()
     t_, G_, _ = O.learn_logistic(1.0, 30.0)
     n = 200
@@ -495,6 +565,8 @@ def main_launchcheck(a):
 
 def main():
     a = parse()
+    if a.dump_outputs and a.workload in ("config1", "dropin", "launchcheck"):
+        raise SystemExit(f"bench.py: --workload {a.workload} returns no per-point arrays to --dump-outputs")
     if a.workload == "launchcheck":
         return main_launchcheck(a)
     if a.workload in ("config1", "config2", "dropin", "multihost"):
@@ -532,7 +604,9 @@ def main():
     p, kappa, lam, x0 = 0.5, 0.6, 0.01, 1e-4
 
     pipe = not a.no_pipeline
-    nbat = max(a.steps, a.warmup, 1) if pipe else 1
+    # every grid of a batch call keeps its own results resident (48 B per point: 0.2 GB per grid at
+    # 2048²), so a run of more than MAX_BATCH steps is timed as several calls over the same rows
+    nbat = min(max(a.steps, a.warmup, 1), MAX_BATCH) if pipe else 1
     # one row per batch (= step); every batch is the full config-3 grid, recomputed
     beta = torch.from_numpy(beta_h).to(dev).repeat(nbat, 1)
     eta = torch.full((nbat, nb), 15.0, dtype=torch.float64, device=dev)
@@ -559,17 +633,22 @@ def main():
 
     def run_steps(n):
         """n steps: one batch call of n grids (learned together, then the
-        equilibria back to back); else one sweep call per step."""
+        equilibria back to back; more than MAX_BATCH steps: a call per MAX_BATCH of them); else
+        one sweep call per step."""
         if n <= 0:
             return
         if pipe:
-            eng.sweep_baseline_batch_dev(beta[:n], eta[:n], t_end[:n], u, p, kappa, lam, x0,
-                                         {k: v[:n] for k, v in out.items()}, stream=stream)
-            if gather:
-                for k0, m in col.windows(n):
-                    eng.batch_wait(comm.cuda_stream, k0 + m - 1)
-                    with torch.cuda.stream(comm):
-                        col.collect(k0, m)
+            for s0 in range(0, n, nbat):
+                c = min(nbat, n - s0)
+                if s0 and comm is not None:  # the rows are reused: the last call's collections first
+                    torch.cuda.current_stream(dev).wait_stream(comm)
+                eng.sweep_baseline_batch_dev(beta[:c], eta[:c], t_end[:c], u, p, kappa, lam, x0,
+                                             {k: v[:c] for k, v in out.items()}, stream=stream)
+                if gather:
+                    for k0, m in col.windows(c):
+                        eng.batch_wait(comm.cuda_stream, k0 + m - 1)
+                        with torch.cuda.stream(comm):
+                            col.collect(k0, m)
         else:
             one = {k: v[0] for k, v in out.items()}
             for k in range(n):
@@ -601,7 +680,7 @@ def main():
 
     # ---- algorithmic flops of this rank's last step (from the kernels' own outputs) ----
     ls = eng.learn_stats(nb)
-    last = (a.steps - 1) if pipe else 0
+    last = (a.steps - 1) % nbat if pipe else 0
     iters = out["iters"][last].cpu().numpy().reshape(nb, nu).astype(np.int64)
     status = out["status"][last].cpu().numpy().view(np.uint32).reshape(nb, nu)
     run = (status & sbr.STATUS["SBR_RUN"]) > 0
@@ -670,6 +749,8 @@ def main():
     if not pipe:
         res["roofline_note"] = "single-sweep mode: chunked kernels overlap; the roofline line is the pipelined default run's"
         res["chunk_timeline_ms"] = [{"learn_end": a, "eq_end": b} for a, b in timeline]
+    if a.dump_outputs:  # before --phases, whose diagnostic sweeps write into grid 0
+        dump_outputs(a.dump_outputs, {k: v[last] for k, v in out.items()}, world, rank)
     if a.phases:
         res["eq_phase_ms"] = phase_breakdown(eng, beta[0], eta[0], t_end[0], u, p, kappa, lam, x0,
                                              {k: v[0] for k, v in out.items()}, stream, dev)
@@ -831,6 +912,8 @@ def main_hetero(a):
                              pmc_of("equilibrium_hetero_kernel<8, 256, 1>", f"hetero_K8_{n}x{n}")),
         "libsbr_sha16": lib_sha(),
     }
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, {k: v[a.steps - 1] for k, v in out_b.items()} if pipe else out, world, rank)
     if a.phases:
         from sbr import _lib
         ph = {}
@@ -978,6 +1061,8 @@ def main_interest(a):
                              pmc_of("equilibrium_kernel<512, true, 1>", f"interest_fig5_{n}x{n}")),
         "libsbr_sha16": lib_sha(),
     }
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, out, world, rank)
     if rank == 0 and world == 1 and not a.no_cpu_baseline:
         sys.path.insert(0, str(REPO / "oracle"))
         import oracle as O  # noqa: E402  (test infrastructure: cpu_baseline leg only)
@@ -1114,6 +1199,8 @@ def main_social(a):
         res["roofline"]["traffic_note"] = ("HBM bytes of the whole share: the PMC run's bytes per attempted RK step "
                                            "(first 16 iterates of the share, tools/pmc_social.py) x this run's RK steps; "
                                            "executed flops count 64 lanes per wave instruction (an upper bound)")
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, out, world, rank)
     if rank == 0 and world == 1 and not a.no_cpu_baseline:
         sys.path.insert(0, str(REPO / "oracle"))
         import oracle as O  # noqa: E402  (test infrastructure: cpu_baseline leg only)

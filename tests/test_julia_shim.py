@@ -218,16 +218,73 @@ def test_dropins_provide_every_field_the_scripts_and_plotting_read(script):
         assert f in structs["SolvedModel"], (script, f)
 
 
-def test_surface_fixture_matches_reference_when_present(tmp_path):
-    """The fixture is what tools/extract_julia_surface.py reads from /root/reference today
-    (skipped where the reference is absent, e.g. on the GPU box).  The extractor writes to a
-    temporary file: the committed fixture is compared, never rewritten."""
-    if not Path("/root/reference/scripts").is_dir():
-        pytest.skip("reference not present")
+SYNTHETIC_TREE = {
+    "src/baseline/model.jl": "struct ModelParameters\n    beta::Float64\n    u::Float64\nend\n",
+    "src/baseline/solver.jl": (
+        "struct SolvedModel\n    xi::Float64\n    bankrun::Bool\nend\n\n"
+        "function solve_learning(params; tol = 1e-6)\n    return (grid = 1, cdf = 2)\nend\n\n"
+        "function solve_equilibrium_baseline(lr, econ; verbose = false, kwargs...)\n"
+        "    result = SolvedModel(1.0, true)\n    return result\nend\n\n"
+        "get_AW(result, t = 0.0) = result.xi + t\n"),
+    "src/baseline/plotting.jl": (
+        "function plot_result(result::SolvedModel, path)\n    (; xi) = result\n    a = get_AW(result)\n"
+        "    return result.bankrun ? xi : a\nend\n"),
+}
+SYNTHETIC_SCRIPT = (
+    'include(joinpath(@__DIR__, "..", "src", "baseline", "model.jl"))\n'
+    'include(joinpath(@__DIR__, "..", "src", "baseline", "solver.jl"))\n'
+    'include(joinpath(@__DIR__, "..", "src", "baseline", "plotting.jl"))\n'
+    "# solve_learning(1, 2, 3) in a comment is no call\n"
+    "lr = solve_learning(m; tol = 1e-8)\n"
+    "res = solve_equilibrium_baseline(lr, m, verbose = true)\n"
+    "println(res.xi, lr.cdf)\n")
+
+
+def test_surface_extractor_on_a_synthetic_tree(tmp_path):
+    """tools/extract_julia_surface.py, which wrote the committed fixture from the reference's
+    files, run on a small Julia tree written here (the reference itself is not part of the
+    repository): includes split into kept and replaced files, definitions with their arities,
+    call sites, return kinds, field reads and struct fields come out as written.  The extractor
+    writes to a temporary file: the committed fixture is never rewritten."""
     import subprocess as sp
 
+    root = (tmp_path / "ref").resolve()
+    for rel, text in SYNTHETIC_TREE.items():
+        (root / rel).parent.mkdir(parents=True, exist_ok=True)
+        (root / rel).write_text(text)
+    (root / "scripts").mkdir()
+    for script in SURFACE:
+        (root / script).write_text(SYNTHETIC_SCRIPT)
     fresh = tmp_path / "julia_surface.json"
-    out = sp.run([sys.executable, str(REPO / "tools" / "extract_julia_surface.py"), str(fresh)], capture_output=True,
-                 text=True)
+    fixture = REPO / "tests" / "golden" / "julia_surface.json"
+    before = fixture.read_bytes()
+    out = sp.run([sys.executable, str(REPO / "tools" / "extract_julia_surface.py"), str(fresh), str(root)],
+                 capture_output=True, text=True)
     assert out.returncode == 0, out.stderr
-    assert fresh.read_text() == (REPO / "tests" / "golden" / "julia_surface.json").read_text()
+    assert fixture.read_bytes() == before
+    got = json.loads(fresh.read_text())
+    assert got["reference"] == str(root) and sorted(got["scripts"]) == sorted(SURFACE)
+    for script, s in got["scripts"].items():
+        assert s["dropins"] == SURFACE[script]["dropins"]
+        assert set(s) == set(SURFACE[script])  # the fixture's sections, all of them
+        assert s["includes"] == ["src/baseline/model.jl", "src/baseline/solver.jl", "src/baseline/plotting.jl"]
+        assert s["keep"] == ["src/baseline/model.jl", "src/baseline/plotting.jl"]
+        assert s["replace"] == ["src/baseline/solver.jl"]
+        sig = {k: [{f: m[f] for f in ("required", "max", "kwargs", "varkw", "line")} for m in v]
+               for k, v in s["defs"].items()}
+        assert sig == {
+            "solve_learning": [dict(required=1, max=1, kwargs=["tol"], varkw=False, line=6)],
+            "solve_equilibrium_baseline": [dict(required=2, max=2, kwargs=["verbose"], varkw=True, line=10)],
+            "get_AW": [dict(required=1, max=2, kwargs=[], varkw=False, line=15)]}
+        assert all(m["file"] == "src/baseline/solver.jl" for v in s["defs"].values() for m in v)
+        assert s["calls"] == [
+            dict(fn="solve_learning", npos=1, kwargs=["tol"], line=5, file=script),
+            dict(fn="solve_equilibrium_baseline", npos=2, kwargs=["verbose"], line=6, file=script),
+            dict(fn="get_AW", npos=1, kwargs=[], line=3, file="src/baseline/plotting.jl")]
+        assert s["returns"] == {"solve_learning": {"namedtuple": ["grid", "cdf"]},
+                                "solve_equilibrium_baseline": {"struct": "SolvedModel"}, "get_AW": None}
+        assert sorted((r["var"], r["fn"], r["field"], r["line"], r["file"]) for r in s["field_reads"]) == [
+            ("lr", "solve_learning", "cdf", 7, script), ("res", "solve_equilibrium_baseline", "xi", 7, script)]
+        assert s["plotting_solvedmodel_reads"] == ["bankrun", "xi"]
+        assert s["structs_replaced"] == {"SolvedModel": {"fields": ["xi", "bankrun"], "file": "src/baseline/solver.jl"}}
+        assert s["structs_kept"] == {"ModelParameters": {"fields": ["beta", "u"], "file": "src/baseline/model.jl"}}

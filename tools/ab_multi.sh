@@ -14,7 +14,7 @@ for rep in $(seq 1 ${REPS:-2}); do
   for v in ${BASE:-base} new ${VARS:-}; do
     L=""; NV="--no-verify"
     [ $v != new ] && L="env SBR_LIB=$VL/$v/libsbr.so"
-    [ $v = new ] && [ $rep = 1 ] && NV=""
+    [ $v = new ] && [ $rep = 1 ] && NV="--full"
     timeout -k 10 300 $L python -u bench.py $D $NV > $OUT/drv_${v}_$rep.out 2>&1 || exit 1
   done
 done

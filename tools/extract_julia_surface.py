@@ -113,5 +113,8 @@ def main(out: Path = OUT):
 
 
 if __name__ == "__main__":
-    # optional output path (default: the committed fixture tests/golden/julia_surface.json)
+    # optional output path (default: the committed fixture tests/golden/julia_surface.json) and
+    # root of the Julia tree to read (default: the reference's)
+    if len(sys.argv) > 2:
+        REF = Path(sys.argv[2]).resolve()
     main(Path(sys.argv[1]) if len(sys.argv) > 1 else OUT)
