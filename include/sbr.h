@@ -390,6 +390,26 @@ int sbr_social_prof_read(sbr_ctx* ctx, int64_t* out8);
 /* Diagnostics of the last social sweep: points promoted into the pool and
  * points re-run from scratch at a larger capacity (either may be NULL). */
 int sbr_social_overflow_stats(sbr_ctx* ctx, int64_t* promoted, int64_t* rerun);
+/* Schedule of the social sweep's iterate launches — same results; for tests and A/B of the
+ * schedule.  A negative argument means the built-in value for that argument.  coop_max >= 0:
+ * live points up to which every point gets a whole wave (built in: 4096); waves >= 1: waves that
+ * share the worklist above that, one point per lane (built in: 1024; never fewer than
+ * ceil(points / 32), the lanes a wave may use); inner >= 1: fixed-point iterates per launch
+ * (built in: 16, 16, then 8).  Stored on the context until changed; an n-device context passes
+ * it on to its children.  SBR_EARG for waves == 0 or inner == 0. */
+int sbr_set_social_schedule(sbr_ctx* ctx, int32_t coop_max, int32_t waves, int32_t inner);
+/* Diagnostics of the last social sweep: point-iterates run in each mode, summed over chunks and
+ * passes — [0] multi-point waves (one point per lane), [1] one-point waves of the main worklist,
+ * [2] promotion-pool waves (an iterate redone in the pool counts in both). */
+int sbr_social_schedule_stats(sbr_ctx* ctx, int64_t* out3);
+/* The launch arithmetic of the iterate kernel for a chunk of n_pts points of which `live` are
+ * unfinished (host code, no device needed; coop_max / waves as in sbr_set_social_schedule):
+ * out4 = {nbs, nmain, L, grid} — waves sharing the worklist, the live count up to which a
+ * point gets a whole wave, lanes used per wave (1: one point per wave), main blocks launched. */
+int sbr_social_plan(int32_t n_pts, int32_t live, int32_t coop_max, int32_t waves, int32_t* out4);
+/* The same plan's L for each of n live counts: lanes[i] = L at live[i] (0 <= live[i] <= n_pts). */
+int sbr_social_plan_lanes(int32_t n_pts, int32_t coop_max, int32_t waves, int64_t n, const int32_t* live,
+                          int32_t* lanes);
 
 /* Interest-rate extension over a β × u grid (one call replaces the loop over
  *     lr = solve_learning(ModelParametersInterest(β_i, η_i, tspan = (0, t_end_i), …).learning)
@@ -436,7 +456,7 @@ void sbr_apply_early_exit(int64_t n_beta, int64_t n_u, int32_t threshold, sbr_re
  * launches as one span (first start to last end, the gaps between them included) that counts
  * as that many calls.  This and the other per-device diagnostics below
  * (sbr_learn_stats, sbr_hetero_learn_stats, sbr_social_prof_read,
- * sbr_social_overflow_stats) return SBR_EARG on an n-device context: call them
+ * sbr_social_overflow_stats, sbr_social_schedule_stats) return SBR_EARG on an n-device context: call them
  * on sbr_multi_child(ctx, rank). */
 int sbr_timing_enable(sbr_ctx* ctx, int on);
 /* The schedule the last single sweep (sbr_sweep_baseline[_dev]) on this device took: 1 = the

@@ -21,6 +21,7 @@
 #include "sbr_hostcopy.h"
 #include "sbr_kernels.h"
 #include "sbr_multi.h"
+#include "sbr_social_plan.h"
 
 // Event flags. Timing events only time (no system-scope cache writeback/invalidate when they
 // complete); dependency events between this device's queues release to device scope.
@@ -69,7 +70,8 @@ struct sbr_ctx {
     int32_t *so_n_old = nullptr, *so_live = nullptr, *so_work[2] = {nullptr, nullptr}, *so_count = nullptr;
     uint32_t *so_slots = nullptr, *so_bits = nullptr;
     int64_t* so_steps = nullptr;
-    // promotion pool (sbr::SocialPool); so_count = [list 0, list 1, pool used, pool live]
+    // promotion pool (sbr::SocialPool); so_count = [list 0, list 1, pool used, pool live] and, from
+    // word 4, three 64-bit counters: point-iterates per mode (sbr_social_schedule_stats)
     size_t pl_slots = 0, pl_cap = 0, pl_cmp = 0;
     double *pl_ws = nullptr, *pl_cmpo = nullptr, *pl_xi = nullptr;
     int32_t *pl_n_old = nullptr, *pl_live = nullptr, *pl_it = nullptr, *pl_ready = nullptr;
@@ -83,6 +85,9 @@ struct sbr_ctx {
     sbr::SocialArgs* so_args_dev = nullptr;  // {main, pool} arguments of the iterate kernel
     sbr::SocialArgs* so_args_host = nullptr; // pinned staging for them
     int64_t so_promoted = 0, so_rerun = 0; // last sweep: points promoted into the pool / re-run larger
+    int64_t so_sched[3] = {0, 0, 0};       // last sweep: point-iterates per mode (multi-point, one-point, pool)
+    // sbr_set_social_schedule (tests and A/B of the schedule; −1: built in)
+    int32_t so_coop_max = -1, so_waves = -1, so_inner = -1;
     int64_t so_budget = 0;            // workspace bytes (0: 60 % of free HBM)
     int64_t* so_prof = nullptr;       // SBR_FLAG_DIAG_SOCIAL_PROF: [pts][8]
     size_t so_prof_pts = 0;
@@ -314,6 +319,9 @@ int ensure_hetero(sbr_ctx* c, size_t n_col, size_t cap, size_t K)
     return ensure_hetero_bufs(c, c->H, c->hs_col, c->hs_cap, c->hs_K, n_col, cap, K);
 }
 
+// so_count: four int32 counters, then the three 64-bit mode counters of the schedule statistics
+constexpr int kSoSched = 4, kSoCountWords = kSoSched + 2 * 3;
+
 void free_social(sbr_ctx* c)
 {
     void* ps[] = {c->so_ws, c->so_cmpo, c->so_xi, c->so_n_old, c->so_live, c->so_work[0], c->so_work[1],
@@ -339,11 +347,11 @@ int ensure_social(sbr_ctx* c, size_t pts, size_t cap, size_t n_cmp)
     HIP_TRY(c, hipMalloc(&c->so_live, pts * 4), SBR_ENOMEM);
     HIP_TRY(c, hipMalloc(&c->so_work[0], pts * 4), SBR_ENOMEM);
     HIP_TRY(c, hipMalloc(&c->so_work[1], pts * 4), SBR_ENOMEM);
-    HIP_TRY(c, hipMalloc(&c->so_count, 8 * 4), SBR_ENOMEM);
+    HIP_TRY(c, hipMalloc(&c->so_count, kSoCountWords * 4), SBR_ENOMEM);
     HIP_TRY(c, hipMalloc(&c->so_slots, pts * 4), SBR_ENOMEM);
     HIP_TRY(c, hipMalloc(&c->so_bits, pts * 4), SBR_ENOMEM);
     HIP_TRY(c, hipMalloc(&c->so_steps, pts * 8), SBR_ENOMEM);
-    if (!c->so_count_host) HIP_TRY(c, hipHostMalloc(&c->so_count_host, 8 * 4), SBR_ENOMEM);
+    if (!c->so_count_host) HIP_TRY(c, hipHostMalloc(&c->so_count_host, kSoCountWords * 4), SBR_ENOMEM);
     if (!c->so_args_dev) HIP_TRY(c, hipMalloc(&c->so_args_dev, 2 * sizeof(sbr::SocialArgs)), SBR_ENOMEM);
     if (!c->so_args_host) HIP_TRY(c, hipHostMalloc(&c->so_args_host, 2 * sizeof(sbr::SocialArgs)), SBR_ENOMEM);
     c->so_pts = pts;
@@ -2222,6 +2230,48 @@ int sbr_social_overflow_stats(sbr_ctx* c, int64_t* promoted, int64_t* rerun)
     return SBR_OK;
 }
 
+int sbr_social_schedule_stats(sbr_ctx* c, int64_t* out3)
+{
+    SBR_PER_DEVICE_DIAG(c);
+    if (!c || !out3) return SBR_EARG;
+    for (int k = 0; k < 3; k++) out3[k] = c->so_sched[k];
+    return SBR_OK;
+}
+
+int sbr_set_social_schedule(sbr_ctx* c, int32_t coop_max, int32_t waves, int32_t inner)
+{
+    if (!c || waves == 0 || inner == 0) return SBR_EARG;
+    for (int r = 0; c->multi && r < sbr_multi_size(c); r++)
+        (void)sbr_set_social_schedule(sbr_multi_child(c, r), coop_max, waves, inner);
+    c->so_coop_max = coop_max < 0 ? -1 : coop_max;
+    c->so_waves = waves < 0 ? -1 : waves;
+    c->so_inner = inner < 0 ? -1 : inner;
+    return SBR_OK;
+}
+
+int sbr_social_plan(int32_t n_pts, int32_t live, int32_t coop_max, int32_t waves, int32_t* out4)
+{
+    if (!out4 || n_pts < 1 || live < 0 || live > n_pts || waves == 0) return SBR_EARG;
+    const sbr::SocialPlan pl = sbr::social_plan(n_pts, coop_max, waves < 0 ? -1 : waves);
+    out4[0] = pl.nbs;
+    out4[1] = pl.nmain;
+    out4[2] = sbr::social_plan_lanes(live, pl.nbs, pl.nmain);
+    out4[3] = pl.nmain; // main blocks of the launch (the promotion pool's blocks follow them)
+    return SBR_OK;
+}
+
+int sbr_social_plan_lanes(int32_t n_pts, int32_t coop_max, int32_t waves, int64_t n, const int32_t* live,
+                          int32_t* lanes)
+{
+    if (n_pts < 1 || waves == 0 || n < 0 || (n > 0 && (!live || !lanes))) return SBR_EARG;
+    const sbr::SocialPlan pl = sbr::social_plan(n_pts, coop_max, waves < 0 ? -1 : waves);
+    for (int64_t i = 0; i < n; i++) {
+        if (live[i] < 0 || live[i] > n_pts) return SBR_EARG;
+        lanes[i] = sbr::social_plan_lanes(live[i], pl.nbs, pl.nmain);
+    }
+    return SBR_OK;
+}
+
 int sbr_set_social_workspace(sbr_ctx* c, int64_t bytes)
 {
     if (!c || bytes < 0) return SBR_EARG;
@@ -2318,6 +2368,7 @@ int run_social_pass(sbr_ctx* c, hipStream_t s, const double* beta, const double*
         a.prof = prof ? c->so_prof : nullptr;
         a.path_t = c->so_path_t; a.path_G = c->so_path_G; a.path_aw = c->so_path_aw; a.path_n = c->so_path_n;
         a.path_cap = c->so_path_cap;
+        a.sched = (unsigned long long*)(c->so_count + kSoSched);
         a.pool = sbr::SocialPool{};
         sbr::SocialArgs b{}; // the pool's own arguments (n_pts = 0: no pool blocks)
         if (nslots > 0) {
@@ -2333,7 +2384,8 @@ int run_social_pass(sbr_ctx* c, hipStream_t s, const double* beta, const double*
             b.it_cur = c->pl_it; b.ready = c->pl_ready; b.n_live = c->so_count + 3;
             HIP_TRY(c, hipMemsetAsync(c->pl_ready, 0, (size_t)nslots * 4, s), SBR_EDEVICE);
         }
-        HIP_TRY(c, hipMemsetAsync(c->so_count + 2, 0, 2 * 4, s), SBR_EDEVICE); // pool allocator + live
+        // pool allocator + live, and this chunk's mode counters
+        HIP_TRY(c, hipMemsetAsync(c->so_count + 2, 0, (kSoCountWords - 2) * 4, s), SBR_EDEVICE);
         // (the staging buffer is reused by the next chunk only after this one's final sync)
         c->so_args_host[0] = a;
         c->so_args_host[1] = b;
@@ -2350,9 +2402,10 @@ int run_social_pass(sbr_ctx* c, hipStream_t s, const double* beta, const double*
         // The first kSocialBulk launches run kSocialInner iterates each (the bulk: most points
         // converge around iterate 35); later launches run kSocialInner2, so the survivors are
         // re-spread over the waves (fewer points per wave, then one: the whole-wave mode) sooner.
+        const int drain_inner = c->so_inner >= 1 ? c->so_inner : kSocialInner;
         std::vector<int> inner;
         for (int done = 0, q = 0; done < max_iter; q++) {
-            const int m = q < kSocialBulk ? kSocialInner : kSocialInner2;
+            const int m = c->so_inner >= 1 ? c->so_inner : (q < kSocialBulk ? kSocialInner : kSocialInner2);
             inner.push_back(m);
             done += m;
         }
@@ -2363,7 +2416,7 @@ int run_social_pass(sbr_ctx* c, hipStream_t s, const double* beta, const double*
         for (; q < n_launch; it += inner[q], q++) {
             const int k = q & 1;
             HIP_TRY(c, sbr::launch_social_iter(a, b, c->so_args_dev, it, inner[q], c->so_work[k],
-                                               c->so_count + k, c->so_work[k ^ 1], c->so_count + (k ^ 1), s),
+                                               c->so_count + k, c->so_work[k ^ 1], c->so_count + (k ^ 1), c->so_coop_max, c->so_waves, s),
                     SBR_EDEVICE);
             if ((poll > 0 || trace) && q + 1 < n_launch) {
                 HIP_TRY(c, hipMemcpyAsync(c->so_count_host, c->so_count, 4 * 4, hipMemcpyDeviceToHost, s),
@@ -2381,13 +2434,13 @@ int run_social_pass(sbr_ctx* c, hipStream_t s, const double* beta, const double*
         // still be live once the main list has reached max_iter: drain launches of kSocialInner
         // iterates run until the pool has no live point (bounded: each advances every pool point
         // by kSocialInner iterates towards max_iter).
-        for (int d = 0; nslots > 0 && d <= max_iter / kSocialInner + 1; d++, it += kSocialInner, q++) {
+        for (int d = 0; nslots > 0 && d <= max_iter / drain_inner + 1; d++, it += drain_inner, q++) {
             HIP_TRY(c, hipMemcpyAsync(c->so_count_host, c->so_count, 4 * 4, hipMemcpyDeviceToHost, s), SBR_EDEVICE);
             HIP_TRY(c, hipStreamSynchronize(s), SBR_EDEVICE);
             if (c->so_count_host[3] == 0) break;
             const int k = q & 1;
-            HIP_TRY(c, sbr::launch_social_iter(a, b, c->so_args_dev, it, kSocialInner, c->so_work[k],
-                                               c->so_count + k, c->so_work[k ^ 1], c->so_count + (k ^ 1), s),
+            HIP_TRY(c, sbr::launch_social_iter(a, b, c->so_args_dev, it, drain_inner, c->so_work[k],
+                                               c->so_count + k, c->so_work[k ^ 1], c->so_count + (k ^ 1), c->so_coop_max, c->so_waves, s),
                     SBR_EDEVICE);
             if (trace)
                 fprintf(stderr, "sbr_social_trace drain=%d pool_live_before=%d\n", d, c->so_count_host[3]);
@@ -2395,8 +2448,14 @@ int run_social_pass(sbr_ctx* c, hipStream_t s, const double* beta, const double*
         tend(c, s, 1, t0);
         // promotions of this chunk (diagnostics), the pool's live count, and the sync that frees
         // the argument staging
-        HIP_TRY(c, hipMemcpyAsync(c->so_count_host + 2, c->so_count + 2, 2 * 4, hipMemcpyDeviceToHost, s), SBR_EDEVICE);
+        HIP_TRY(c, hipMemcpyAsync(c->so_count_host + 2, c->so_count + 2, (kSoCountWords - 2) * 4, hipMemcpyDeviceToHost, s),
+                SBR_EDEVICE);
         HIP_TRY(c, hipStreamSynchronize(s), SBR_EDEVICE);
+        for (int m = 0; m < 3; m++) {
+            int64_t v;
+            memcpy(&v, c->so_count_host + kSoSched + 2 * m, 8);
+            c->so_sched[m] += v;
+        }
         // the drain is bounded by max_iter; a pool point still live past it would leave its results
         // unwritten — never returned as if solved
         if (nslots > 0 && c->so_count_host[3] != 0)
@@ -2432,6 +2491,7 @@ int run_social(sbr_ctx* c, hipStream_t s, const double* beta, const double* eta,
     if (cap > (size_t)kSocialMaxCap) cap = (size_t)kSocialMaxCap;
     c->so_prof_acc.assign(8, 0);
     c->so_promoted = c->so_rerun = 0;
+    c->so_sched[0] = c->so_sched[1] = c->so_sched[2] = 0;
     int rc = run_social_pass(c, s, beta, eta, x0, u, n_u, p, kappa, lambda, cmp, n_cmp, tol, max_iter, o, out,
                              fp_iters, rk_steps, poll, cap, pool_cap(cap), nullptr, n_total);
     if (rc) return rc;

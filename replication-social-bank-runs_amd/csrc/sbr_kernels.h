@@ -187,6 +187,9 @@ struct SocialArgs {
     int32_t* it_cur;
     int32_t* ready;
     int32_t* n_live;
+    // point-iterates run per mode (sbr_social_schedule_stats): [0] multi-point lanes, [1] one-point
+    // waves of the main worklist, [2] pool waves (may be null)
+    unsigned long long* sched;
     // single-point path mode: the learning knots of every iterate's equilibrium (the
     // returned SolvedModel's are the last written); path_n = knots (−knots if > path_cap)
     double* path_t;
@@ -199,10 +202,11 @@ struct SocialArgs {
 hipError_t launch_social_init(const SocialArgs& a, hipStream_t s);
 // n_inner iterates (from `iter`) over `work`/`count` plus every published pool
 // slot (`p`, n_pts = 0: no pool), then the ordered compaction of the main
-// worklist into work_out; args_dev holds {a, p} in device memory
+// worklist into work_out; args_dev holds {a, p} in device memory; coop_max / waves < 0: the
+// built-in schedule (sbr_social_plan.h)
 hipError_t launch_social_iter(const SocialArgs& a, const SocialArgs& p, const SocialArgs* args_dev, int iter,
                               int n_inner, const int32_t* work, const int32_t* count, int32_t* work_out,
-                              int32_t* count_out, hipStream_t s);
+                              int32_t* count_out, int coop_max, int waves, hipStream_t s);
 
 // phase 0: learning (+ the streamed hazards); 1: equilibria; 2: the hazards of knots and group
 // CDFs already in L (n_knots and status set by the caller)

@@ -29,6 +29,7 @@
 #include "sbr_device.h"
 #include "sbr_kernels.h"
 #include "sbr_ode.h"
+#include "sbr_social_plan.h"
 
 namespace sbr {
 
@@ -423,7 +424,7 @@ __device__ void coop_damping(BView T, BView Gv, BView AWO, const int n, const do
 
 constexpr int kRing = 64; // knots per lane: four 16-knot lines (two lines per lane for 64 lanes was slower: r04_z)
 
-constexpr int kRingLanes = 32; // lanes a multi-point wave may use (the launch makes L <= this)
+// kRingLanes (sbr_social_plan.h): lanes a multi-point wave may use (the plan makes L <= this)
 constexpr size_t kRingLdsBytes = (size_t)2 * kRing * kRingLanes * sizeof(double); // t and v: 32 KiB either way
 
 // dG/dt = (1 − G) β AW_old(t) (social_learning_dynamics.jl:61-67) for a wave that runs many
@@ -1260,6 +1261,13 @@ __device__ __forceinline__ bool social_iterate(const SocialArgs& a, int l, int i
     return true;
 }
 
+// sbr_social_schedule_stats: one relaxed atomic per point-iterate (>= 10⁴ RK steps) on the
+// counter of the mode that runs it; in the one-point modes lane 0 counts for its wave
+__device__ __forceinline__ void sched_count(const SocialArgs& a, int mode, bool mine)
+{
+    if (a.sched && mine) __hip_atomic_fetch_add(a.sched + mode, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
 // ============================================================================
 // up to n_inner fixed-point iterates for every live point of the worklist
 // ============================================================================
@@ -1271,10 +1279,7 @@ __device__ __forceinline__ bool social_iterate(const SocialArgs& a, int l, int i
 // picked up here or by the next launch; either way it redoes that iterate).
 // args[0]: the main worklist's arguments, args[1]: the pool's (n_pts = 0: none),
 // in device memory so that the wave-uniform choice between them stays scalar loads.
-constexpr int kSocialWaves = 1024; // one wave per SIMD (2048 waves, two per SIMD, were slower: r04_u)
-// live points up to which every point gets a whole wave (SocialRhsCoop), in rounds of the
-// kSocialWaves resident ones, instead of ⌈live/kSocialWaves⌉ points per wave
-constexpr int kSocialCoopMax = 4096;
+// kSocialWaves, kSocialCoopMax and the arithmetic of nbs / nmain / L: sbr_social_plan.h.
 // Main blocks (one wave each) spread the live worklist over all `nbs` of them: L = ⌈live/nbs⌉
 // consecutive entries per wave (L ≤ 64), lanes ≥ L idle.  A fixed-point lane's RK step is a
 // serial chain whose memory side grows with the wave's active lanes (each lane streams its own
@@ -1293,19 +1298,16 @@ __global__ __launch_bounds__(64, 1) void social_iter_kernel(const SocialArgs* __
     if (!in_pool) {
         const int cnt = *count;
         // at most nmain live points: one per wave (coop), beyond that the first nbs waves
-        int L = cnt <= nmain ? 1 : (cnt + nbs - 1) / nbs;
-        // the ring holds kRingLanes lanes: the host's nbs = ⌈n_pts / kRingLanes⌉ >= ⌈cnt / kRingLanes⌉
-        // keeps L within it; the clamp stops a future change of that arithmetic from letting lanes
-        // share ring slots (which in_ring() would trust)
-        constexpr int kLmax = kRingLanes;
-        L = L < 1 ? 1 : (L > kLmax ? kLmax : L);
+        const int L = social_plan_lanes(cnt, nbs, nmain);
         if (L == 1) { // one point per wave: the whole wave runs it
             const int w = blockIdx.x;
             if (w >= cnt) return;
             l = work[w];
             if (!sa.live[l]) return;
-            for (int k = 0; k < n_inner; k++)
+            for (int k = 0; k < n_inner; k++) {
+                sched_count(sa, 1, (threadIdx.x & 63) == 0);
                 if (!social_iterate<true>(sa, l, iter_arg + k, s_ring)) break;
+            }
             return;
         }
         if ((int)threadIdx.x >= L || (int)blockIdx.x >= nbs) return;
@@ -1322,13 +1324,17 @@ __global__ __launch_bounds__(64, 1) void social_iter_kernel(const SocialArgs* __
         if (__hip_atomic_load(pa.ready + l, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) == 0) return;
         if (!pa.live[l]) return;
         iter = pa.it_cur[l];
-        for (int k = 0; k < n_inner; k++)
+        for (int k = 0; k < n_inner; k++) {
+            sched_count(pa, 2, (threadIdx.x & 63) == 0);
             if (!social_iterate<true>(pa, l, iter + k, s_ring)) break;
+        }
         return;
     }
     const SocialArgs& a = args[in_pool ? 1 : 0];
-    for (int k = 0; k < n_inner; k++)
+    for (int k = 0; k < n_inner; k++) {
+        sched_count(a, 0, true);
         if (!social_iterate<false>(a, l, iter + k, s_ring)) break;
+    }
 }
 
 // ============================================================================
@@ -1382,17 +1388,11 @@ hipError_t launch_social_init(const SocialArgs& a, hipStream_t s)
 
 hipError_t launch_social_iter(const SocialArgs& a, const SocialArgs& p, const SocialArgs* args_dev, int iter,
                               int n_inner, const int32_t* work, const int32_t* count, int32_t* work_out,
-                              int32_t* count_out, hipStream_t s)
+                              int32_t* count_out, int coop_max, int waves, hipStream_t s)
 {
-    // main blocks: one wave per SIMD of the MI355X (4 × 256), at least one wave per 64 points
-    // and no more than one per point
-    int nbs = (a.n_pts + kRingLanes - 1) / kRingLanes; // L = ⌈live / nbs⌉ <= kRingLanes (the ring's lanes)
-    nbs = nbs > kSocialWaves ? nbs : kSocialWaves;
-    nbs = nbs < a.n_pts ? nbs : (a.n_pts > 0 ? a.n_pts : 1);
+    const SocialPlan plan = social_plan(a.n_pts, coop_max, waves);
+    const int nbs = plan.nbs, nmain = plan.nmain;
     const int pool_waves = p.n_pts;
-    // main blocks: nbs multi-point waves, or up to kSocialCoopMax one-point waves
-    const int coop_max = kSocialCoopMax < a.n_pts ? kSocialCoopMax : a.n_pts;
-    const int nmain = nbs > coop_max ? nbs : coop_max;
     hipLaunchKernelGGL(social_iter_kernel, dim3(nmain + pool_waves), dim3(64), kRingLdsBytes, s,
                        args_dev, iter, n_inner, work, count, nbs, nmain);
     hipError_t e = hipGetLastError();

@@ -16,6 +16,8 @@ from .engine import (  # noqa: F401
     SolvedModelHetero,
     SolvedModelInterest,
     get_AW_functions_interest,
+    social_plan,
+    social_plan_lanes,
     solve_equilibrium_baseline,
     solve_equilibrium_hetero,
     solve_SInetwork_hetero,

@@ -123,6 +123,10 @@ _SIGS = {
     "sbr_set_social_workspace": (ctypes.c_int, [_P, _I64]),
     "sbr_social_prof_read": (ctypes.c_int, [_P, _P]),
     "sbr_social_overflow_stats": (ctypes.c_int, [_P, _P, _P]),
+    "sbr_set_social_schedule": (ctypes.c_int, [_P, _I32, _I32, _I32]),
+    "sbr_social_schedule_stats": (ctypes.c_int, [_P, _P]),
+    "sbr_social_plan": (ctypes.c_int, [_I32, _I32, _I32, _I32, _P]),
+    "sbr_social_plan_lanes": (ctypes.c_int, [_I32, _I32, _I32, _I64, _P, _P]),
     "sbr_social_point_paths": (ctypes.c_int, [_P, _D, _D, _D, _D, _D, _D, _D, _P, ctypes.c_int32, _D,
                                               ctypes.c_int32, _P, _P, _P, _P, _P, _P, _P, _I64, _P]),
     "sbr_learn_hetero": (ctypes.c_int, [_P, _I32, _P, _P, _P, _D, _I64, _P, _P, _P, _I64, _P, _P]),

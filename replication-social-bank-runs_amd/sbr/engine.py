@@ -18,6 +18,7 @@ There is no CPU fallback: without libsbr.so or a GPU every call raises.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes
 import os
 from dataclasses import dataclass, field
@@ -593,6 +594,31 @@ class Engine:
               "sbr_social_overflow_stats")
         return dict(promoted=a.value, rerun=b.value)
 
+    def set_social_schedule(self, coop_max: int = -1, waves: int = -1, inner: int = -1) -> None:
+        """Launch schedule of the following social sweeps (sbr_set_social_schedule — same
+        results; for tests and A/B of the schedule).  A negative argument means the built-in
+        value: ``coop_max`` live points up to which a point gets a whole wave (4096), ``waves``
+        that share the worklist above that (1024), ``inner`` fixed-point iterates per launch."""
+        check(self._L.sbr_set_social_schedule(self._ctx, coop_max, waves, inner), self._ctx,
+              "sbr_set_social_schedule")
+
+    @contextlib.contextmanager
+    def social_schedule(self, coop_max: int = -1, waves: int = -1, inner: int = -1):
+        """``with engine.social_schedule(0, 1, 1): ...`` — set_social_schedule for the block,
+        the built-in schedule again on the way out (also when the block raises)."""
+        self.set_social_schedule(coop_max, waves, inner)
+        try:
+            yield self
+        finally:
+            self.set_social_schedule()
+
+    def social_schedule_stats(self) -> list[int]:
+        """Last social sweep: point-iterates run by [0] multi-point waves (one point per lane),
+        [1] one-point waves of the main worklist, [2] promotion-pool waves."""
+        v = (ctypes.c_int64 * 3)()
+        check(self._L.sbr_social_schedule_stats(self._ctx, v), self._ctx, "sbr_social_schedule_stats")
+        return list(v)
+
     def device_info(self) -> dict:
         a, b, c = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32()
         check(self._L.sbr_device_info(self._ctx, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c)), self._ctx,
@@ -676,6 +702,25 @@ def default_engine() -> Engine:
     if _default is None:
         _default = Engine()
     return _default
+
+
+def social_plan(n_pts: int, live: int, coop_max: int = -1, waves: int = -1) -> dict:
+    """Launch arithmetic of the social iterate kernel for a chunk of ``n_pts`` points with
+    ``live`` unfinished (sbr_social_plan: host code, no GPU needed): ``nbs`` waves that share
+    the worklist, ``nmain`` live points up to which a point gets a whole wave, ``L`` lanes used
+    per wave (1: one point per wave), ``grid`` main blocks.  Negative: the built-in schedule."""
+    v = (ctypes.c_int32 * 4)()
+    check(_lib.load().sbr_social_plan(n_pts, live, coop_max, waves, v), None, "sbr_social_plan")
+    return dict(nbs=v[0], nmain=v[1], L=v[2], grid=v[3])
+
+
+def social_plan_lanes(n_pts: int, live, coop_max: int = -1, waves: int = -1) -> np.ndarray:
+    """social_plan's ``L`` for every entry of ``live`` (sbr_social_plan_lanes)."""
+    live = np.ascontiguousarray(live, np.int32)
+    lanes = np.empty(live.shape, np.int32)
+    check(_lib.load().sbr_social_plan_lanes(n_pts, coop_max, waves, live.size, _ptr(live), _ptr(lanes)), None,
+          "sbr_social_plan_lanes")
+    return lanes
 
 
 # ---------------------------------------------------------------------------
