@@ -927,80 +927,143 @@ __device__ __forceinline__ void solve_from_buffers(P T, P G, P H, const Summ& S,
     double c_ic_x = NAN, c_ic_v = 0.0;
     uint32_t s = SBR_NO_RUN_MAXITER;
     double xi = NAN, tolr = INFINITY;
-    // Single-interval bisection.  Once the bracket is one knot interval [t0, t1) (jlo == jhi),
-    // G(ξ) there is the line g0·(1 − δ) + g1·δ, and the error AW − κ of a midpoint is
-    // e0 + s·(x − t0) up to a few ulps of the operands.  Every midpoint whose estimate is
-    // farther than `lim` from zero has the sign of its estimate and is no terminal iterate
-    // (|AW − κ| > tol): it moves xmin or xmax without the search, the lerp and its division.
-    // Only the last few midpoints (|err| ≲ 1e-13) run the exact iteration below.  The
-    // exact iteration's other effects are constant over the interval (ic = tin, oc = ξ,
-    // ε = t1 − t0, the BoundsError tests of ξ + ε and tin + ε pass), checked on entry.
-    // ea = s·x + c (c = e0 − s·t0, |s·t0| ≤ 16: the rounding of c and of the fma stays ≈1e-14, far
-    // inside lim); f_s = NaN until the interval is reached: every comparison fails and the exact
-    // iteration runs.  Lanes of a wave move through the same trips, the decided ones skipping
-    // the exact body.
-    double f_s = NAN, f_c = 0.0;
-    const double f_lim = tolerance + 1e-13;
-    for (int iter = 1; iter <= max_iters; iter++) {
-        r.iters = iter;
-        const double dd = xmin - xmax;
-        if (collapsed(dd)) { s = SBR_NO_RUN_COLLAPSE; break; }
-        if (iter == max_iters - 1) { s = SBR_NO_RUN_MAXITER; break; }
-        const double xo = xnew;
-        {
-            const double ea = fma(f_s, xo, f_c);
-            if (ea < -f_lim) { xmin = xo; xnew = 0.5 * (xo + xmax); continue; }
-            if (ea > f_lim) { xmax = xo; xnew = 0.5 * (xo + xmin); continue; }
-        }
-        const double ic = dmin(tin, xo), oc = dmin(tout, xo);
-        const int j = ssl_range(T, jlo, jhi, xo); // t[jlo] <= ξmin <= xo <= ξmax < t[jhi+1]
-        // G(oc)
-        bool ok = in_range(oc, tlo, thi, trunc, flag);
-        int joc = (oc == xo) ? j : (ok ? ssl_range(T, 0, n - 1, oc) : 0);
-        const double Goc = ok ? lerp_at(T, G, n, joc, oc) : 0.0;
-        // G(ic) — ic == tin for every iterate of a valid bracket; cached by value
-        double Gic = 0.0;
-        int jic = 0;
-        if (in_range(ic, tlo, thi, trunc, flag)) {
-            jic = (ic == tin) ? jtin : (ic == xo ? j : ssl_range(T, 0, n - 1, ic));
-            if (ic == c_ic_x) Gic = c_ic_v;
-            else { Gic = lerp_at(T, G, n, jic, ic); c_ic_x = ic; c_ic_v = Gic; }
-        }
-        // ε = local knot spacing at ξ_old (solver.jl:336-338)
-        if (j + 1 >= n) { flag |= trunc ? SBR_ENGINE_TRUNC : SBR_OOB; break; }
-        const double eps = T[j + 1] - T[j];
-        const double xoe = oc + eps, xie = ic + eps;
-        // the slope probe AW(ξ + ε) only decides the terminal iterate (solver.jl:345-352);
-        // its lookups' BoundsError checks still run every iterate, in the reference's order
-        const bool oke = in_range(xoe, tlo, thi, trunc, flag);
-        const bool oki = in_range(xie, tlo, thi, trunc, flag);
-        if (flag) break;
-        const double AW = Goc - Gic;
-        const double err = AW - kappa;
-        if (fabs(err) <= tolerance) {
-            double Goce = 0.0, Gice = 0.0;
-            if (oke) Goce = lerp_at(T, G, n, ssl_gallop(T, n, joc, xoe), xoe);
-            if (oki) Gice = lerp_at(T, G, n, ssl_gallop(T, n, jic, xie), xie);
-            const double AWe = Goce - Gice;
-            if (AWe >= AW) { s = SBR_RUN; xi = xo; tolr = fabs(err); }
-            else s = SBR_FALSE_EQ;
-            break;
-        } else if (err > 0) {
-            xmax = xo; jhi = j; xnew = 0.5 * (xo + xmin);
-        } else {
-            xmin = xo; jlo = j; xnew = 0.5 * (xo + xmax);
-        }
-        if (f_s != f_s && jlo == jhi && ic == tin && tin <= xmin && xmax <= tout && xmax + eps <= thi) {
-            // j + 1 < n and ξ + ε, tin + ε in range were tested by this iteration
-            const double t0 = T[j], g0 = G[j], g1 = G[j + 1];
-            const double mag = dmax(dmax(fabs(g0), fabs(g1)), dmax(fabs(Gic), fabs(kappa)));
-            if (mag <= 4.0 && eps > 0.0) { // finite, moderate operands (NaN fails): rounding ≤ 1e-14
-                const double sl = (g1 - g0) / eps, st = sl * t0;
-                if (fabs(st) <= 16.0) { // |c| ≤ 28: its rounding stays ≈1e-14
-                    f_s = sl;
-                    f_c = ((g0 - Gic) - kappa) - st;
+    // The bisection runs in two loops.
+    // Loop A is the reference's iteration, every lookup bracketed by [jlo, jhi].  Once a lane's
+    // bracket is one knot interval [t0, t1) (jlo == jhi) and the tests below hold, every later
+    // iterate of that lane is decided by constants (`single`): ξmin and ξmax only move inward,
+    // so tin ≤ ξmin ≤ ξ ≤ ξmax ≤ tout gives ic = tin and oc = ξ (in range, as tin and tout are),
+    // the search over [jlo, jhi] returns j = jlo, ε = t1 − t0, G(ic) is the cached G(tin), and the
+    // BoundsError tests pass: tin + ε was tested by the iteration that set `single`, and
+    // tlo ≤ ξ + ε ≤ ξmax + ε ≤ thi because rounding is monotone.  A `single` lane that stays in
+    // loop A runs the same operations as before.
+    // When every lane of the wave still iterating is `single`, the wave moves to loop B, which
+    // iterates on registers alone: δ = (ξ − t0)/ε, G(ξ) = g0·(1 − δ) + g1·δ, err = (G(ξ) − G(tin)) − κ,
+    // the same operations in the reference's order, without the search, the range tests or LDS.
+    // A wave holding a lane that never becomes `single` (a bracket at the end of the grid, NaN
+    // buffers) stays in loop A until that lane terminates.  Iteration counts, ξ and every status
+    // bit are the reference's.
+    // Both arguments need midpoints that stay inside [ξmin, ξmax]: 0.5·(a + b) does for a <= b
+    // (monotone rounding) unless a + b overflows, so the grid has to be of moderate size.
+    // Loop A itself is specialised for an ordered bracket (ORD: tin <= tout on a moderate grid,
+    // every lane of the wave): there tin = ξmin <= ξ <= ξmax = tout from the first iterate on, so
+    // ic = tin and oc = ξ, both pass their range tests (tin and tout did), G(oc) is looked up
+    // at j and G(ic) = G(tin) once; the ε probes' range tests stay (they fail near the end of the
+    // grid).  Any other wave (a last 1→0 crossing before the first 0→1 one) runs the iteration as
+    // the reference writes it.
+    const bool moderate = tlo >= -0x1p1000 && thi <= 0x1p1000;
+    bool single = false, live = false;
+    int iter = 1;
+    auto loop_a = [&](auto spec) {
+        constexpr bool ORD = decltype(spec)::value;
+        if constexpr (ORD) c_ic_v = lerp_at(T, G, n, jtin, tin);
+        for (; iter <= max_iters; iter++) {
+            r.iters = iter;
+            const double dd = xmin - xmax;
+            if (collapsed(dd)) { s = SBR_NO_RUN_COLLAPSE; break; }
+            if (iter == max_iters - 1) { s = SBR_NO_RUN_MAXITER; break; }
+            const double xo = xnew;
+            const int j = ssl_range(T, jlo, jhi, xo); // t[jlo] <= ξmin <= xo <= ξmax < t[jhi+1]
+            double ic, oc, Goc, Gic = 0.0;
+            int joc, jic = 0;
+            if constexpr (ORD) {
+                ic = tin; oc = xo; joc = j; jic = jtin;
+                Goc = lerp_at(T, G, n, j, xo);
+                Gic = c_ic_v;
+            } else {
+                ic = dmin(tin, xo); oc = dmin(tout, xo);
+                // G(oc)
+                const bool ok = in_range(oc, tlo, thi, trunc, flag);
+                joc = (oc == xo) ? j : (ok ? ssl_range(T, 0, n - 1, oc) : 0);
+                Goc = ok ? lerp_at(T, G, n, joc, oc) : 0.0;
+                // G(ic) — ic == tin for every iterate of a valid bracket; cached by value
+                if (in_range(ic, tlo, thi, trunc, flag)) {
+                    jic = (ic == tin) ? jtin : (ic == xo ? j : ssl_range(T, 0, n - 1, ic));
+                    if (ic == c_ic_x) Gic = c_ic_v;
+                    else { Gic = lerp_at(T, G, n, jic, ic); c_ic_x = ic; c_ic_v = Gic; }
                 }
             }
+            // ε = local knot spacing at ξ_old (solver.jl:336-338)
+            if (j + 1 >= n) { flag |= trunc ? SBR_ENGINE_TRUNC : SBR_OOB; break; }
+            const double eps = T[j + 1] - T[j];
+            const double xoe = oc + eps, xie = ic + eps;
+            // the slope probe AW(ξ + ε) only decides the terminal iterate (solver.jl:345-352);
+            // its lookups' BoundsError checks still run every iterate, in the reference's order
+            const bool oke = in_range(xoe, tlo, thi, trunc, flag);
+            const bool oki = in_range(xie, tlo, thi, trunc, flag);
+            if (flag) break;
+            const double AW = Goc - Gic;
+            const double err = AW - kappa;
+            if (fabs(err) <= tolerance) {
+                double Goce = 0.0, Gice = 0.0;
+                if (oke) Goce = lerp_at(T, G, n, ssl_gallop(T, n, joc, xoe), xoe);
+                if (oki) Gice = lerp_at(T, G, n, ssl_gallop(T, n, jic, xie), xie);
+                const double AWe = Goce - Gice;
+                if (AWe >= AW) { s = SBR_RUN; xi = xo; tolr = fabs(err); }
+                else s = SBR_FALSE_EQ;
+                break;
+            } else if (err > 0) {
+                xmax = xo; jhi = j; xnew = 0.5 * (xo + xmin);
+            } else {
+                xmin = xo; jlo = j; xnew = 0.5 * (xo + xmax);
+            }
+            // j + 1 < n and ξ + ε, tin + ε in range were tested by this iteration (ε > 0: t[j] <= ξ < t[j+1])
+            const bool inside = ORD || (moderate && ic == tin && tin <= xmin && xmax <= tout);
+            single = single || (inside && jlo == jhi && xmax + eps <= thi && eps > 0.0);
+            if (__ballot(!single) == 0) { live = true; iter++; break; }
+        }
+    };
+    if (__ballot(!(moderate && tin <= tout)) == 0) loop_a(BoolC<true>{});
+    else loop_a(BoolC<false>{});
+    if (live) {
+        const int j = jlo;
+        const double t0 = T[j], g0 = G[j], g1 = G[j + 1], eps = T[j + 1] - t0, Gic = c_ic_v;
+        // ε is the same for every iterate, so its reciprocal is refined once and the quotient
+        // takes div_rcp's three operations.  That is the IEEE quotient (sbr_device.h) where
+        // v_div_scale and v_div_fixup are identities: here the divisor ε is in [2^-64, 2^64] and the
+        // dividend a = ξ − t0 is 0 or in [2^-900, ε] (a <= ξmax − t0 <= t1 − t0 by monotone
+        // rounding), so the quotient and the remainder term are normal numbers or 0.  a >= 2^-900
+        // when nonzero: for |t0| >= 2^-840 either |ξ| < |t0|/2 or the signs differ (a >= |t0|/2),
+        // or ξ − t0 is exact (Sterbenz) and a multiple of ulp(t0)/2 >= 2^-894; for t0 = 0, a = ξ >=
+        // ξmin, which must already be >= 2^-900 — a bracket [0, ·) can halve towards 0 for as many
+        // iterations as the caller's bisect_max_iters allows, and then keeps `/`.  One lane
+        // outside these ranges sends its wave through the loop with `/`.
+        // (The estimate e0 + s·(ξ − t0) that used to skip the exact body of decided midpoints does
+        // not pay any more: in this loop it was slower, as was `/` for every wave —
+        // profiles/experiments/r07_bisect_loops.json.)
+        const bool rcp_ok = eps >= 0x1p-64 && eps <= 0x1p64 &&
+                            (fabs(t0) >= 0x1p-840 || (t0 == 0.0 && xmin >= 0x1p-900));
+        const bool use_rcp = __ballot(!rcp_ok) == 0;
+        const double rinv = rcp_refined(eps);
+        const int last = max_iters - 1;
+        int ex = 0; // 1 collapse, 2 iteration cap, 3 terminal iterate; 0: the loop ran out
+        double xo = xnew, err = 0.0, Goc = 0.0;
+        auto trips = [&](auto quot) {
+            for (; iter <= max_iters; iter++) {
+                r.iters = iter;
+                const bool col = collapsed(xmin - xmax);
+                xo = xnew;
+                const double d = quot(xo - t0);
+                Goc = g0 * (1.0 - d) + g1 * d;
+                err = (Goc - Gic) - kappa;
+                const bool ter = fabs(err) <= tolerance;
+                if (col || iter == last || ter) { ex = col ? 1 : (iter == last ? 2 : 3); break; }
+                const bool up = err > 0;
+                const double other = up ? xmin : xmax;
+                xmax = up ? xo : xmax;
+                xmin = up ? xmin : xo;
+                xnew = 0.5 * (xo + other);
+            }
+        };
+        if (use_rcp) trips([&](double a) { return div_rcp(a, eps, rinv); });
+        else trips([&](double a) { return a / eps; });
+        if (ex == 1) s = SBR_NO_RUN_COLLAPSE;
+        else if (ex == 3) {
+            // the terminal iterate's slope probe (both arguments in range, see above)
+            const double xoe = xo + eps, xie = tin + eps, AW = Goc - Gic;
+            const double Goce = lerp_at(T, G, n, ssl_gallop(T, n, j, xoe), xoe);
+            const double Gice = lerp_at(T, G, n, ssl_gallop(T, n, jtin, xie), xie);
+            if (Goce - Gice >= AW) { s = SBR_RUN; xi = xo; tolr = fabs(err); }
+            else s = SBR_FALSE_EQ;
         }
     }
     if (flag) { r.status = flag | lbits; return; }

@@ -52,6 +52,12 @@ constexpr double DBL_EPS = 2.220446049250313e-16;
 // (d = ±0 or ±denorm_min); NaN and ±Inf fail both forms.
 __device__ __forceinline__ bool collapsed(double d) { return fabs(d) <= 4.9406564584124654e-324; }
 
+// a compile-time bool as a value: the argument of a generic lambda specialised with `if constexpr`
+template <bool B>
+struct BoolC {
+    static constexpr bool value = B;
+};
+
 __device__ __forceinline__ double dmin(double a, double b) { return a < b ? a : b; }
 __device__ __forceinline__ double dmax(double a, double b) { return a > b ? a : b; }
 // One v_min_f64 / v_max_f64 (IEEE minNum / maxNum) instead of a compare and two
