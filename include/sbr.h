@@ -193,6 +193,40 @@ int sbr_set_batch_workspace(sbr_ctx* ctx, int64_t bytes);
 int sbr_batch_wait(sbr_ctx* ctx, void* stream, int64_t k);
 
 /*
+ * A list of models — n independent points, each with its own seven parameters (a cross-section
+ * of banks, the draws of a calibration, the samples of a sensitivity analysis):
+ *     point i = solve_learning(LearningParameters(beta[i], (0, t_end[i]), x0))                 learning.jl:109
+ *             + solve_equilibrium_baseline(lr, EconomicParameters(u[i], p[i], kappa[i], lambda[i], η_bar, eta[i]))
+ *             + get_AW_functions!(r).AW_max                                  solver.jl:413, 553-576
+ * exactly what sbr_sweep_baseline gives for n_beta = n_u = 1 at those values.  Seven input
+ * arrays of n doubles; every out field has n entries (iters may be NULL).  Every point is learned
+ * on a lane of its own: points are not de-duplicated (two points with the same β, η and t_end
+ * integrate the same ODE twice) — a flattened β × u grid belongs to the sweep entry points above.
+ * A point that breaks a rule of model.jl:31-35, 71-76 (β > 0, t_end > 0, η > 0, u >= 0,
+ * 0 <= p <= 1, 0 < κ < 1, λ > 0; a NaN breaks its rule) ends with status == SBR_ARG_INVALID,
+ * ξ = τ̄_IN = τ̄_OUT = AW_max = NaN, tol = Inf, iters = 0, and no other point is touched.
+ * SBR_EARG: x0 < 0, n < 0, a null array (with n > 0), SBR_FLAG_XI_GUESS.  n == 0 is SBR_OK and
+ * writes nothing.  opts->early_exit_nan_run is ignored (a list has no columns).  Host pointers;
+ * synchronous; a failed call writes none of the caller's arrays.  On an n-device context the
+ * points are dealt cyclically (point i to device i mod n_gpus), over either transport.
+ * The learning workspace counts 4 × knot_capacity × 8 + 24 bytes per point; a list larger than
+ * the budget (sbr_set_points_workspace) runs in chunks through the same workspace, in stream
+ * order, and the results do not depend on the chunking.
+ */
+int sbr_solve_points(sbr_ctx* ctx, const double* beta, const double* eta, const double* t_end, double x0,
+                     const double* u, const double* p, const double* kappa, const double* lambda, int64_t n,
+                     const sbr_opts* opts, sbr_result_soa* out);
+/* Same on device pointers (the seven arrays and every out field in HBM), enqueued on `stream`;
+ * no host synchronisation.  Needs a single-device context. */
+int sbr_solve_points_dev(sbr_ctx* ctx, void* stream, const double* beta, const double* eta, const double* t_end,
+                         double x0, const double* u, const double* p, const double* kappa, const double* lambda,
+                         int64_t n, const sbr_opts* opts, sbr_result_soa* out);
+/* Budget in bytes for the learning workspace of sbr_solve_points[_dev] (0 = 40 % of the free plus
+ * already held HBM at call time): it caps the points per chunk.  An allocation that fails anyway
+ * halves the chunk and retries, down to one point.  An n-device context sets every rank's budget. */
+int sbr_set_points_workspace(sbr_ctx* ctx, int64_t bytes);
+
+/*
  * Learning only — solve_learning (learning.jl:109-124) for n_beta β at once.
  * Writes, per β, the knot grid t and CDF values G of the adaptive ODE
  * solution (row i at [i*cap .. i*cap + n_knots[i]) ); g = βG(1−G) is implied

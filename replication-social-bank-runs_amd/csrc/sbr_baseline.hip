@@ -17,9 +17,12 @@
 //
 // Bit-exact against oracle/sbr_oracle.c (see sbr_device.h).
 #include "sbr_device.h"
+#include "sbr_hazard_dev.h"
 #include "sbr_kernels.h"
 #include "sbr_ode.h"
+#include "sbr_point_dev.h"
 #include "sbr_scan.h"
+#include "sbr_solve_dev.h"
 
 namespace sbr {
 
@@ -316,262 +319,6 @@ __global__ __launch_bounds__(HN_BLOCK) void hazard_norm_kernel(LearnArgs a, Lear
 // e = exp(λτ̄)·g, the cumulative trapezoid (sequential, in the reference's
 // order) and HR = (p·exp(λτ̄))·g / (p·I + (1−p)·I_η).
 // ============================================================================
-constexpr int kEqWide = 768; // lanes per equilibrium workgroup on wide u tiles
-constexpr int kEqMinW = 6;    // waves per SIMD the baseline equilibrium kernel must fit (two 12-wave blocks per CU)
-constexpr int HZ_BLOCK = 256;
-constexpr int HZ_LDS = 1024; // τ̄ knots per LDS chunk of the hazard kernel
-constexpr int HZ_REG = 16;   // τ̄ knots per thread held in registers (ntau <= 4096: one pass over HBM)
-constexpr int EQ_TILE = 4096; // u values per equilibrium block (one block per β column up to this)
-constexpr int kAwWin = 6;     // 8-blocks each side of the predicted AW peak evaluated first
-
-// I_k = I_{k-1} + term_k over s_I[0, cn) in place, left to right (the reference's rounding
-// order), by the 64 lanes of one wave: lane l holds terms [16l, 16l + 16) in registers and
-// the running integral passes from lane to lane — in round r only lane r adds (16 dependent
-// adds), then v_readlane broadcasts its I.  The chain is the adds plus one broadcast per 16
-// terms; a one-lane scan out of LDS waits on an LDS round trip every few terms instead.
-// Call with all 64 lanes of the wave active; I must be wave-uniform (and is on return).
-constexpr int HZ_LANE = HZ_LDS / 64; // terms per lane (16)
-__device__ __forceinline__ double hz_bcast(double x, int lane)
-{
-    const uint64_t u = sbr_dbits(x);
-    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)u, lane);
-    const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(u >> 32), lane);
-    return sbr_bitsd(((uint64_t)hi << 32) | lo);
-}
-__device__ __forceinline__ void hz_scan_wave(double* s_I, int cn, double& I)
-{
-    const int lane = threadIdx.x & 63, base = lane * HZ_LANE;
-    double v[HZ_LANE];
-#pragma unroll
-    for (int j = 0; j < HZ_LANE; j++) v[j] = base + j < cn ? s_I[base + j] : 0.0;
-    const int rounds = (cn + HZ_LANE - 1) / HZ_LANE;
-    double acc = I;
-    for (int r = 0; r < rounds; r++) {
-        if (lane == r) {
-            // the tail past cn adds +0.0, which leaves I (>= +0) unchanged
-#pragma unroll
-            for (int j = 0; j < HZ_LANE; j++) { acc = acc + v[j]; v[j] = acc; }
-        }
-        acc = hz_bcast(acc, r);
-    }
-    I = acc;
-#pragma unroll
-    for (int j = 0; j < HZ_LANE; j++)
-        if (base + j < cn) s_I[base + j] = v[j];
-}
-
-#ifdef SBR_HZ_PROF // per-block phase cycles of the hazard kernel (tools/ubench_hazard.hip)
-__device__ long long g_hzprof[8192 * 6];
-#define HZ_T0 long long hz_tp = __builtin_amdgcn_s_memtime()
-#define HZ_STAMP(ph)                                                                                  \
-    do {                                                                                              \
-        const long long hz_now = __builtin_amdgcn_s_memtime();                                        \
-        if (threadIdx.x == 0) g_hzprof[(size_t)blockIdx.x * 6 + (ph)] += hz_now - hz_tp;              \
-        hz_tp = hz_now;                                                                               \
-    } while (0)
-#else
-#define HZ_T0
-#define HZ_STAMP(ph)
-#endif
-// hazard_rate of column b by one workgroup of NT >= HZ_BLOCK threads (threads past HZ_BLOCK
-// only take part in the barriers): the τ̄ grid in chunks of HZ_LDS knots, e_i·g_i and the
-// trapezoid terms formed in parallel into LDS, one wave adds the terms left to right (the
-// reference's rounding order), and a last parallel pass turns the partial integrals into
-// HR_i.  LDS scratch: s_eg, s_t [HZ_LDS + 1], s_I [HZ_LDS], s_Ieta [1].  Every early
-// return is uniform over the workgroup.
-template <int NT, bool REGS = true>
-__device__ __forceinline__ void hazard_column(const int b, const double BETA, const double ETA, const LearnArgs& a,
-                                              const LearnBufs& L, double* s_eg, double* s_t, double* s_I,
-                                              double* s_Ieta)
-{
-    static_assert(NT >= HZ_BLOCK, "hazard_column needs HZ_BLOCK threads");
-    const int tid = threadIdx.x;
-    const bool act = tid < HZ_BLOCK;
-    HZ_T0;
-    const int n = L.n_knots[b];
-    const uint32_t st = L.status[b];
-    if (st & SBR_ARG_INVALID) return; // learn kernel already wrote the row
-    const size_t row = (size_t)b * (size_t)L.cap;
-    const double* __restrict__ T = L.t + row;
-    const double* __restrict__ Gv = L.G + row;
-    double* __restrict__ H = L.hr + row;
-    const double p = a.p, lam = a.lam;
-    const int m = L.n_le[b]; // #knots ≤ η (searchsortedlast + 1), counted by the learning kernel
-    bool oob = false, push;
-    if (m < n) {
-        push = (m == 0) || T[m - 1] != ETA; // solver.jl:159
-        oob = (m == 0);                       // pdf(η) with η < t_0
-    } else {
-        push = (m == 0) || T[m - 1] != ETA;
-        oob = push;                           // no knot beyond η to interpolate pdf(η)
-    }
-    const int ntau = m + (push ? 1 : 0);
-    if (oob) {
-        if (tid == 0) {
-            L.status[b] = st | SBR_OOB;
-            L.n_tau[b] = 0;
-            L.n_le[b] = 0;
-        }
-        return;
-    }
-    // the pdf at knot i: compute_pdf_symbolic_baseline's βG(1 − G) (learning.jl:161-173), or the
-    // caller's values (a.pdf: the interpolant of another pdf on the same knots)
-    const double* __restrict__ PD = a.pdf ? a.pdf + row : nullptr; // the caller's pdf rows, laid out like G
-    auto pdf_k = [&](int i) -> double {
-        if (PD) return PD[i];
-        const double x = Gv[i];
-        return (BETA * x) * (1.0 - x);
-    };
-    auto pdf_at = [&](int i) -> double {
-        if (i < m) return pdf_k(i);
-        // η on bracket [m-1, m]
-        const double g0 = pdf_k(m - 1);
-        const double g1 = pdf_k(m);
-        const double d = (ETA - T[m - 1]) / (T[m] - T[m - 1]);
-        return g0 * (1.0 - d) + g1 * d;
-    };
-    auto tau_at = [&](int i) -> double { return i < m ? T[i] : ETA; };
-    // Global reads are batched (unrolled loops, every load of a batch in flight before the
-    // first use): the knots were written by another XCD's learning wave, so each one costs an
-    // L2 miss, and one dependent miss per knot per thread would dominate the kernel.
-    HZ_STAMP(0);
-    if (REGS && ntau <= HZ_BLOCK * HZ_REG) {
-        // Every τ̄ knot of the column in registers (thread tid owns knots tid + 256·j): one
-        // batch of global loads, the chunks fed to LDS from registers, I_i read back into
-        // registers, HR written once.
-        double tv[HZ_REG], egv[HZ_REG], numv[HZ_REG], iv[HZ_REG], gk[HZ_REG];
-        if (act) {
-            // loads first, unconditionally (indices clamped into the knots ≤ η), so that all of
-            // them are in flight at once; τ̄ = η and its interpolated pdf are selected after
-            const double pdf_eta = m < n ? pdf_at(m) : 0.0; // m == n: η is a knot, not pushed
-#pragma unroll
-            for (int j = 0; j < HZ_REG; j++) {
-                const int i = tid + HZ_BLOCK * j;
-                const int ic = i < m ? i : m - 1;
-                tv[j] = T[ic];
-                gk[j] = PD ? PD[ic] : Gv[ic];
-            }
-#pragma unroll
-            for (int j = 0; j < HZ_REG; j++) {
-                const int i = tid + HZ_BLOCK * j;
-                const double x = gk[j];
-                const double ti = i < m ? tv[j] : ETA;
-                const double g = i < m ? (PD ? x : (BETA * x) * (1.0 - x)) : pdf_eta;
-                const double E = sbr_exp(lam * ti);
-                tv[j] = ti;
-                egv[j] = E * g;        // e_i = exp(λτ̄_i)·pdf_i
-                numv[j] = (p * E) * g; // the HR numerator (p·exp(λτ̄_i))·pdf_i
-                iv[j] = 0.0;
-            }
-        }
-        double I = 0.0;
-        constexpr int RPC = HZ_LDS / HZ_BLOCK; // register slots per LDS chunk
-#pragma unroll
-        for (int c = 0; c < HZ_REG / RPC; c++) {
-            const int c0 = c * HZ_LDS;
-            if (c0 < ntau) { // uniform
-                const int cn = ntau - c0 < HZ_LDS ? ntau - c0 : HZ_LDS;
-                if (act) {
-#pragma unroll
-                    for (int r = 0; r < RPC; r++) {
-                        const int k = tid + HZ_BLOCK * r;
-                        s_t[k + 1] = tv[c * RPC + r];
-                        s_eg[k + 1] = egv[c * RPC + r];
-                    }
-                    if (c > 0 && tid == HZ_BLOCK - 1) { // knot c0 − 1 is this thread's last slot
-                        s_t[0] = tv[c * RPC - 1];
-                        s_eg[0] = egv[c * RPC - 1];
-                    }
-                }
-                __syncthreads();
-                HZ_STAMP(1);
-                if (act)
-                    for (int k = tid; k < cn; k += HZ_BLOCK)
-                        s_I[k] = c0 + k == 0 ? 0.0 : (0.5 * (s_eg[k] + s_eg[k + 1])) * (s_t[k + 1] - s_t[k]);
-                __syncthreads();
-                HZ_STAMP(2);
-                if (tid < 64) hz_scan_wave(s_I, cn, I);
-                __syncthreads();
-                HZ_STAMP(3);
-                if (act) {
-#pragma unroll
-                    for (int r = 0; r < RPC; r++) {
-                        const int k = tid + HZ_BLOCK * r;
-                        if (k < cn) iv[c * RPC + r] = s_I[k];
-                    }
-                }
-                __syncthreads(); // the chunk's LDS is reused
-                HZ_STAMP(4);
-            }
-        }
-        if (tid == 0) {
-            s_Ieta[0] = I;
-            L.n_tau[b] = ntau;
-            L.n_le[b] = m;
-        }
-        __syncthreads();
-        const double Ieta = s_Ieta[0], omp = 1.0 - p;
-        if (act) {
-#pragma unroll
-            for (int j = 0; j < HZ_REG; j++) {
-                const int i = tid + HZ_BLOCK * j;
-                if (i < ntau) H[i] = numv[j] / ((p * iv[j]) + (omp * Ieta));
-            }
-        }
-        HZ_STAMP(5);
-        return;
-    }
-    double I = 0.0, egprev = 0.0, tprev = 0.0; // thread 0: running integral; the chunk's last e·g, τ̄
-    for (int c0 = 0; c0 < ntau; c0 += HZ_LDS) {
-        const int cn = ntau - c0 < HZ_LDS ? ntau - c0 : HZ_LDS;
-        if (tid == 0) { s_eg[0] = egprev; s_t[0] = tprev; }
-        if (act) {
-#pragma unroll 4
-            for (int k = tid; k < cn; k += HZ_BLOCK) {
-                const int i = c0 + k;
-                const double ti = tau_at(i);
-                s_t[k + 1] = ti;
-                s_eg[k + 1] = sbr_exp(lam * ti) * pdf_at(i); // e_i = exp(λτ̄_i)·pdf_i
-            }
-        }
-        __syncthreads();
-        HZ_STAMP(1);
-        // trapezoid term of i pairs e_{i-1}, e_i (solver.jl:173-175); term_0 = 0
-        if (act)
-            for (int k = tid; k < cn; k += HZ_BLOCK)
-                s_I[k] = c0 + k == 0 ? 0.0 : (0.5 * (s_eg[k] + s_eg[k + 1])) * (s_t[k + 1] - s_t[k]);
-        __syncthreads();
-        HZ_STAMP(2);
-        if (tid < 64) hz_scan_wave(s_I, cn, I); // I_i = I_{i-1} + term_i, left to right
-        if (tid == 0) {
-            egprev = s_eg[cn];
-            tprev = s_t[cn];
-        }
-        __syncthreads();
-        HZ_STAMP(3);
-        if (act)
-            for (int k = tid; k < cn; k += HZ_BLOCK) H[c0 + k] = s_I[k]; // I_i parked in the HR row
-        __syncthreads(); // the chunk's LDS is reused
-        HZ_STAMP(4);
-    }
-    if (tid == 0) {
-        s_Ieta[0] = I;
-        L.n_tau[b] = ntau;
-        L.n_le[b] = m;
-    }
-    __syncthreads();
-    // HR_i = (p·exp(λτ̄_i))·pdf_i / (p·I_i + (1 − p)·I_η); each thread reads back the I_i it parked
-    const double Ieta = s_Ieta[0], omp = 1.0 - p;
-    if (act) {
-#pragma unroll 4
-        for (int i = tid; i < ntau; i += HZ_BLOCK) {
-            const double E = sbr_exp(lam * tau_at(i));
-            H[i] = ((p * E) * pdf_at(i)) / ((p * H[i]) + (omp * Ieta));
-        }
-    }
-    HZ_STAMP(5);
-}
-
 __global__ __launch_bounds__(HZ_BLOCK) void hazard_kernel(const double* __restrict__ beta,
                                                           const double* __restrict__ eta, LearnArgs a, LearnBufs L)
 {
@@ -589,252 +336,6 @@ __global__ __launch_bounds__(HZ_BLOCK) void hazard_kernel(const double* __restri
 // ============================================================================
 // Equilibrium kernel
 // ============================================================================
-struct PointResult {
-    double xi, tin, tout, aw, tol;
-    uint32_t status;
-    int iters;
-};
-
-// range check of an interpolation argument; returns false (and flags) when
-// Interpolations' Throw() extrapolation would raise.
-__device__ __forceinline__ bool in_range(double x, double tlo, double thi, bool trunc, uint32_t& flag)
-{
-    if (x >= tlo && x <= thi) return true;
-    flag |= (trunc && x > thi) ? SBR_ENGINE_TRUNC : SBR_OOB;
-    return false;
-}
-
-// Per-workgroup summaries staged in LDS next to the knot grid (null = unavailable):
-//   hmax/hmin  per 64-entry block of HR(τ̄): max over non-NaN entries / min with NaN as −∞,
-//              i.e. "some entry > u" ⇔ hmax > u and "every entry > u" ⇔ hmin > u;
-//   pmc/smc    per 64-knot block of G: prefix max / suffix min over blocks (NaN-propagating).
-struct Summ {
-    const double* hmax;
-    const double* hmin;
-    const double* pmc;
-    const double* smc;
-    bool mono; // G nondecreasing over the knots (no NaN): prefix max / suffix min are knot values
-    double t_half; // time where G crosses 1/2 (lerp inverse), NaN if it does not: AW peak predictor
-    // aw_scan's preconditions: no NaN in G, 0 <= G[0], G[n−1] <= 2 (the 1e-14 rounding margin),
-    // t[k+2] − t[k] > 1e-15·t[n−1] (a shifted τ̄ argument stays below the knot after next) and a
-    // drawdown bound dd <= 1e-12 (Tsit5 at eps() leaves ulp-sized decreases in the saturated tail
-    // of G on ≈20 % of the Fig 5 columns: G[k] <= G[k'] + dd for every k < k')
-    bool scan;
-    double dd;
-    bool bnb; // the branch-and-bound bounds are available (mono, or the prefix/suffix tables built)
-    // aw_scan's knot offset for AW_OUT(b_j) <= G[j + koff]: 1 when consecutive knots are more than
-    // 1e-15·t[n−1] apart (b_j then lies below t[j + 1]: bracket <= j), else 2 (knots 2 apart)
-    int koff;
-    // prefix / suffix extremes of the HR block summaries: hpm = prefix max of hmax,
-    // hpn = prefix min of hmin, hsm = suffix max of hmax, hsn = suffix min of hmin, over nbh
-    // blocks; null: the linear block scans
-    const double* hpm;
-    const double* hpn;
-    const double* hsm;
-    const double* hsn;
-    int nbh;
-};
-
-template <class P>
-__device__ __forceinline__ void solve_from_buffers(P T, P G, P H, const Summ& S, const int n, const int ntau,
-                                                   const int nle, const double ETA, const double T1, const bool trunc,
-                                                   const double u, const double kappa, const int max_iters,
-                                                   const uint32_t lbits, PointResult& r, double* __restrict__ aw_path,
-                                                   const int diag, const double tin, const double tout);
-
-// smallest k in [0, hi] with key(k) >= x, for a nondecreasing key with key(hi) >= x: gallop
-// down from hi, then bisect
-template <class F>
-__device__ __forceinline__ int first_ge_down(F key, int hi, double x)
-{
-    int top = hi, lo = hi - 1, step = 1; // key(top) >= x; answer in (lo, top]
-    while (lo >= 0 && key(lo) >= x) {
-        top = lo;
-        step <<= 1;
-        lo = top - step;
-    }
-    if (lo < -1) lo = -1;
-    while (top - lo > 1) {
-        const int mid = (lo + top) >> 1;
-        if (key(mid) >= x) top = mid;
-        else lo = mid;
-    }
-    return top;
-}
-
-// AW_max (solver.jl:553-576) over τ̄ knots [0, ntau) by an outward scan from the predicted
-// peak knot c, for a G with Summ::scan's preconditions (nondecreasing up to the drawdown dd:
-// every bound below is widened by dd, and the margin is 1e-14 + 4·dd).  AW_cum(τ̄_i) =
-// AW_OUT(b_i) − AW_IN(a_i) + G(0) with a_i = (τ̄_i − ξ) + icc ≤ b_i = (τ̄_i − ξ) + occ ≤ τ̄_i + ulp,
-// both nondecreasing in i, so
-//   right of the last evaluated knot i:  AW_OUT(b_j) ≤ G[j + 2] and AW_IN(a_j) ≥ AW_IN(a_i);
-//   left of it:                         AW_OUT(b_j) ≤ AW_OUT(b_i) and AW_IN(a_j) ≥ G[bracket(a_j)].
-// A knot is evaluated exactly (the same operations as eval_range) only where these bounds
-// (+ the 1e-14 rounding margin) do not already put it at or below the running maximum; runs
-// of knots the bounds dismiss are skipped with one search in G (right) or in G and τ̄ (left).
-// The maximum equals the exhaustive one bit for bit (G has no NaN here).
-// (A knot offset 0 for the AW_OUT bound inside [ξ/2, 2ξ], where b_i = t[i] exactly, halved the exact
-// evaluations and was slower: an exact evaluation costs about what a bounded trip costs,
-// profiles/experiments/r05_d_*)
-template <class P>
-__device__ __forceinline__ void aw_scan(P T, P G, const int n, const int ntau, const int nle, const double ETA,
-                                        const double xi, const double icc, const double occ, const double G0,
-                                        const double dd, const int c, double& mx, int& nev, const int koff = 2)
-{
-    const double M = 1e-14 + 4.0 * dd;
-    auto tau = [&](int i) -> double { return i < nle ? T[i] : ETA; };
-    auto av_of = [&](int i) -> double { return (tau(i) - xi) + icc; };
-    // a(τ̄_i)'s bracket window: k = min(searchsortedlast(t, x), n − 2), its two knots (t, G)
-    int ka;
-    double ta0, ta1, ga0, ga1;
-    auto seek = [&](int hint, double x) {
-        ka = ssl_near(T, n, hint, x);
-        ka = ka < n - 2 ? ka : n - 2;
-        ta0 = T[ka]; ta1 = T[ka + 1]; ga0 = G[ka]; ga1 = G[ka + 1];
-    };
-    auto fwd = [&](double x) {
-        while (ka < n - 2 && ta1 <= x) { ka++; ta0 = ta1; ga0 = ga1; ta1 = T[ka + 1]; ga1 = G[ka + 1]; }
-    };
-    auto bwd = [&](double x) {
-        while (ka > 0 && ta0 > x) { ka--; ta1 = ta0; ga1 = ga0; ta0 = T[ka]; ga0 = G[ka]; }
-    };
-    // exact AW_cum(τ̄_i) with the a window at a_i's bracket; b's bracket is searched from i
-    double awin = 0.0, awout = 0.0;
-    auto exact = [&](int i, double av, double xa) -> double {
-        const double ti = tau(i);
-        const double bv = (ti - xi) + occ;
-        const double xb = bv > 0 ? bv : 0.0;
-        // b(τ̄_i) is τ̄_i = t[i] itself whenever τ̄_i − ξ is exact: bracket i, no search
-        int kb = (i < nle && xb == ti) ? i : ssl_near(T, n, i, xb);
-        kb = kb < n - 2 ? kb : n - 2;
-        const double tb0 = T[kb], tb1 = T[kb + 1], gb0 = G[kb], gb1 = G[kb + 1];
-        const double da = (xa - ta0) / (ta1 - ta0);
-        const double gi = ga0 * (1.0 - da) + ga1 * da;
-        double go;
-        if (xb == tb0) go = gb0 * 1.0 + gb1 * 0.0;
-        else { const double db = (xb - tb0) / (tb1 - tb0); go = gb0 * (1.0 - db) + gb1 * db; }
-        awin = av >= 0 ? gi : 0.0;
-        awout = bv >= 0 ? go : 0.0;
-        nev++;
-        return (awout - awin) + G0;
-    };
-    // knot c
-    {
-        const double av = av_of(c), xa = av > 0 ? av : 0.0;
-        seek(c, xa);
-        const double v = exact(c, av, xa);
-        if (v > mx) mx = v;
-    }
-    const int kc = ka;
-    const double ub_left = awout;
-    // right of c
-    double LA = awin; // lower bound of AW_IN(a_j) for every j >= i
-    for (int i = c + 1; i < ntau;) {
-        const double ti = tau(i);
-        const double av = (ti - xi) + icc, xa = av > 0 ? av : 0.0;
-        fwd(xa);
-        const double lb = av >= 0 ? ga0 : 0.0;
-        LA = LA > lb ? LA : lb;
-        const double V = (((mx - G0) + LA) - M) - dd; // G[k] <= V: every knot up to k is <= V + dd
-        const int k2 = i + koff < n - 1 ? i + koff : n - 1;
-        if (G[k2] > V) {
-            const double v = exact(i, av, xa);
-            if (v > mx) mx = v;
-            LA = awin;
-            i++;
-            continue;
-        }
-        // every knot j with G[min(j + 2, n − 1)] <= V is at or below mx: skip to the first other
-        const int kl = ssl_gallop(G, n, k2, V);
-        if (kl >= n - 1) break;
-        // G[kl + 1] > V: the first knot whose bound is not dismissed
-        const int inext = kl + 1 - koff;
-        const double an = av_of(inext);
-        seek(ka + (inext - i), an > 0 ? an : 0.0);
-        i = inext;
-    }
-    // left of c
-    double UB = ub_left; // upper bound of AW_OUT(b_j) for every j <= i
-    {
-        const double av = av_of(c);
-        seek(kc, av > 0 ? av : 0.0);
-    }
-    for (int i = c - 1; i >= 0;) {
-        const double ti = tau(i);
-        const int k2 = i + koff < n - 1 ? i + koff : n - 1;
-        const double g2 = G[k2] > 0.0 ? G[k2] : 0.0;
-        UB = UB < g2 ? UB : g2;
-        const double Vp = (((UB + G0) + M) - mx) + dd; // AW_IN(a_j) >= G[bracket(a_j)] − dd
-        if (!(Vp - dd > 0.0)) break; // AW_IN(a_j) >= 0 for every j: all pruned
-        const double av = (ti - xi) + icc, xa = av > 0 ? av : 0.0;
-        bwd(xa);
-        const double lb = av >= 0 ? ga0 : 0.0;
-        if (!(lb >= Vp)) {
-            const double v = exact(i, av, xa);
-            if (v > mx) mx = v;
-            UB = UB < awout ? UB : awout;
-            i--;
-            continue;
-        }
-        // knots j <= i with a_j >= t[k*] (k* = first knot with G >= Vp) are pruned
-        const int ks = first_ge_down([&](int k) { return G[k]; }, ka, Vp);
-        const double tk = T[ks];
-        const int j = first_ge_down(av_of, i, tk);
-        if (j == 0) break;
-        const int inext = j - 1;
-        const double an = av_of(inext);
-        seek(ks, an > 0 ? an : 0.0);
-        i = inext;
-    }
-}
-
-// compute_ξ (solver.jl:308-376) from an arbitrary first iterate ξ_guess (the single-point kernel's
-// knots-in calls only: the sweep kernel carries none of this): the reference's iteration as
-// written, every lookup bracketed by a search over the whole grid (the oracle's compute_xi).  A
-// lookup outside [t[0], t[n−1]] — G at a constrained time, searchsortedlast(grid, ξ_old) below the
-// first knot or at the last, the ε probes — is the interpolant's BoundsError.
-template <class P>
-__device__ __forceinline__ void bisect_plain(P T, P G, const int n, const double tlo, const double thi,
-                                             const bool trunc, const double tin, const double tout,
-                                             const double guess, const double kappa, const double tolerance,
-                                             const int max_iters, PointResult& r, uint32_t& flag, uint32_t& s,
-                                             double& xi, double& tolr)
-{
-    double xnew = guess, xmin = tin, xmax = tout;
-    for (int iter = 1; iter <= max_iters; iter++) {
-        r.iters = iter;
-        if (collapsed(xmin - xmax)) { s = SBR_NO_RUN_COLLAPSE; return; }
-        if (iter == max_iters - 1) { s = SBR_NO_RUN_MAXITER; return; }
-        const double xo = xnew;
-        const double ic = dmin(tin, xo), oc = dmin(tout, xo);
-        double Goc = 0.0, Gic = 0.0;
-        if (in_range(oc, tlo, thi, trunc, flag)) Goc = lerp_at(T, G, n, ssl_range(T, 0, n - 1, oc), oc);
-        if (in_range(ic, tlo, thi, trunc, flag)) Gic = lerp_at(T, G, n, ssl_range(T, 0, n - 1, ic), ic);
-        if (!(xo >= tlo)) { flag |= SBR_OOB; return; } // searchsortedlast = 0: grid[0]
-        const int j = ssl_range(T, 0, n - 1, xo);
-        if (j + 1 >= n) { flag |= trunc ? SBR_ENGINE_TRUNC : SBR_OOB; return; }
-        const double eps = T[j + 1] - T[j];
-        const double xoe = oc + eps, xie = ic + eps;
-        const bool oke = in_range(xoe, tlo, thi, trunc, flag);
-        const bool oki = in_range(xie, tlo, thi, trunc, flag);
-        if (flag) return;
-        const double AW = Goc - Gic;
-        const double err = AW - kappa;
-        if (fabs(err) <= tolerance) {
-            double Goce = 0.0, Gice = 0.0;
-            if (oke) Goce = lerp_at(T, G, n, ssl_range(T, 0, n - 1, xoe), xoe);
-            if (oki) Gice = lerp_at(T, G, n, ssl_range(T, 0, n - 1, xie), xie);
-            if (Goce - Gice >= AW) { s = SBR_RUN; xi = xo; tolr = fabs(err); }
-            else s = SBR_FALSE_EQ;
-            return;
-        } else if (err > 0) {
-            xmax = xo; xnew = 0.5 * (xo + xmin);
-        } else {
-            xmin = xo; xnew = 0.5 * (xo + xmax);
-        }
-    }
-}
-
 template <class P>
 __device__ __forceinline__ void solve_point(P T, P G, P H, const Summ& S, const int n, const int ntau,
                                             const int nle, const double ETA, const double T1, const bool trunc,
@@ -1808,264 +1309,6 @@ __global__ __launch_bounds__(kEqWide, kEqMinW) void eq_ready_kernel(LearnBufs L,
 // solve_from_buffers' exact iteration and eval_range (each lookup lands on the bracket
 // ssl_range finds: the knots are sorted), so the same bits.
 // ============================================================================
-constexpr int CO_BLOCK = 256;
-
-// searchsortedlast in [lo, hi] (ssl_range's result for sorted t: lo + #{j in (lo, hi] : t[j] <= x})
-// by the 64 lanes of a wave; every lane returns the same index.  Call with the whole wave active.
-template <class P>
-__device__ __forceinline__ int wave_ssl(P t, int lo, int hi, double x)
-{
-    const int lane = threadIdx.x & 63;
-    if (lo >= hi) return lo; // a one-knot bracket (most bisection iterates once narrowed)
-    while (hi - lo > 64) {
-        const int step = (hi - lo + 63) >> 6; // probes lo + k·step, k = 1..64 (those <= hi)
-        const int pk = lo + (lane + 1) * step;
-        const bool pr = pk <= hi && t[pk <= hi ? pk : hi] <= x;
-        const int c = __popcll(__ballot(pr)); // the true probes are a prefix (t sorted)
-        const int nhi = lo + (c + 1) * step - 1;
-        hi = nhi < hi ? nhi : hi;
-        lo = lo + c * step;
-    }
-    const int pk = lo + 1 + lane;
-    const bool pr = pk <= hi && t[pk <= hi ? pk : hi] <= x;
-    return lo + __popcll(__ballot(pr));
-}
-
-// lane k's double (k wave-uniform)
-__device__ __forceinline__ double co_rl(double x, int k)
-{
-    const uint64_t u = sbr_dbits(x);
-    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)u, k);
-    const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(u >> 32), k);
-    return sbr_bitsd(((uint64_t)hi << 32) | lo);
-}
-
-// wave-uniform in_range (the flag as solve_from_buffers sets it)
-__device__ __forceinline__ bool co_in_range(double x, double tlo, double thi, bool trunc, uint32_t& flag)
-{
-    if (x >= tlo && x <= thi) return true;
-    flag |= (trunc && x > thi) ? SBR_ENGINE_TRUNC : SBR_OOB;
-    return false;
-}
-
-template <class P>
-__device__ __forceinline__ void point_wave(P T, P G, P H, const int n, const int ntau, const int nle,
-                                           const double ETA, const double T1, const bool trunc, const double u,
-                                           const double kappa, const int max_iters, const uint32_t lbits,
-                                           PointResult& r, const double guess)
-{
-    const int lane = threadIdx.x & 63;
-    r.xi = NAN; r.aw = NAN; r.tol = INFINITY; r.iters = 0; r.status = 0;
-    // ---------------- optimal_buffer (solver.jl:211-264), 64 τ̄ entries per round ----------------
-    bool any = false, all = true;
-    int fa = -1, la = -1, cin = -1, cout = -1;
-    for (int b0 = 0; b0 < ntau; b0 += 64) {
-        const int i = b0 + lane;
-        const bool in = i < ntau;
-        const bool ab = in && H[in ? i : 0] > u;
-        const bool pv = in && i > 0 && H[i > 0 && in ? i - 1 : 0] > u;
-        const unsigned long long mab = __ballot(ab), min_ = __ballot(in);
-        any |= mab != 0ull;
-        all &= (mab & min_) == min_;
-        if (mab) {
-            if (fa < 0) fa = b0 + __ffsll((long long)mab) - 1;
-            la = b0 + 63 - __clzll((long long)mab);
-        }
-        const unsigned long long mi = __ballot(in && i > 0 && !pv && ab); // 0 → 1 at i: cin = i − 1
-        const unsigned long long mo = __ballot(in && i > 0 && pv && !ab); // 1 → 0 at i: cout = i − 1
-        if (cin < 0 && mi) cin = b0 + __ffsll((long long)mi) - 2;
-        if (mo) cout = b0 + 63 - __clzll((long long)mo) - 1;
-    }
-    auto tau = [&](int i) -> double { return i < nle ? T[i] : ETA; };
-    double tin, tout;
-    if (!any) {
-        tin = T1; tout = T1;
-    } else if (all) {
-        tin = tau(0); tout = tau(ntau - 1);
-    } else {
-        tin = T1; tout = T1;
-        if (cin >= 0) {
-            const double t0 = tau(cin), t1 = tau(cin + 1), h0 = H[cin], h1 = H[cin + 1];
-            tin = t0 + ((u - h0) * (t1 - t0)) / (h1 - h0);
-        }
-        if (cout >= 0) {
-            const double t0 = tau(cout), t1 = tau(cout + 1), h0 = H[cout], h1 = H[cout + 1];
-            tout = t0 + ((u - h0) * (t1 - t0)) / (h1 - h0);
-        }
-        if (tin == T1) tin = tau(fa);
-        if (tout == T1) tout = tau(la);
-    }
-    r.tin = tin;
-    r.tout = tout;
-    const double tlo = T[0], thi = T[n - 1];
-    if (tin == tout) {
-        r.status = SBR_NO_RUN_HR_BELOW_U | SBR_CONVERGED | lbits;
-        r.tol = 0.0;
-        return;
-    }
-    // ---------------- compute_ξ (solver.jl:308-376): the exact iteration ----------------
-    uint32_t flag = 0;
-    const double tolerance = 10.0 * sbr_jl_eps(kappa);
-    uint32_t s = SBR_NO_RUN_MAXITER;
-    double xi = NAN, tolr = INFINITY;
-    if (guess == guess) { // ξ_guess: the plain iteration (solve_from_buffers), wave-uniform
-        bisect_plain(T, G, n, tlo, thi, trunc, tin, tout, guess, kappa, tolerance, max_iters, r, flag, s, xi, tolr);
-    } else {
-    double xnew = (tin + tout) / 2.0, xmin = tin, xmax = tout;
-    const bool okmin = co_in_range(xmin, tlo, thi, trunc, flag);
-    const bool okmax = co_in_range(xmax, tlo, thi, trunc, flag);
-    if (!okmin || !okmax) { r.status = flag | lbits; return; }
-    int jlo = wave_ssl(T, 0, n - 1, xmin);
-    int jhi = wave_ssl(T, 0, n - 1, xmax);
-    const int jtin = jlo;
-    // Rounds of six bisection levels at once: lane ℓ < 63 evaluates node k = ℓ + 1 of the
-    // depth-6 tree below the current state (heap order; child 2k follows err > 0, 2k + 1
-    // err < 0), replaying its path's midpoint arithmetic exactly, then the wave walks the tree
-    // with the nodes' signs.  Each node runs the serial iteration's tests in its order; the walk
-    // stops at the first terminal node on the path — the iteration where the serial loop breaks,
-    // with its counters, flags and (for |err| <= tol) the slope probe, done by the whole wave.
-    int iter0 = 1;
-    for (;;) {
-        const int k = lane + 1;
-        const int d = 31 - __builtin_clz(k);
-        double nmin = xmin, nmax = xmax, xo = xnew;
-        for (int b = d - 1; b >= 0; b--) {
-            if (((k >> b) & 1) == 0) { nmax = xo; xo = 0.5 * (xo + nmin); }
-            else { nmin = xo; xo = 0.5 * (xo + nmax); }
-        }
-        const int it = iter0 + d;
-        int term = 0; // 1 collapse, 2 max_iters − 1, 3 range flag, 4 |err| <= tol, 5 past max_iters
-        uint32_t nflag = 0;
-        double err = 0.0, AW = 0.0, oc = 0.0, ic = 0.0, xoe = 0.0, xie = 0.0;
-        int j = 0, joc = 0, jic = 0;
-        bool oke = false, oki = false;
-        if (lane < 63) {
-            if (it > max_iters) term = 5;
-            else if (collapsed(nmin - nmax)) term = 1;
-            else if (it == max_iters - 1) term = 2;
-            else {
-                ic = dmin(tin, xo); oc = dmin(tout, xo);
-                j = ssl_range(T, jlo, jhi, xo);
-                const bool ok = co_in_range(oc, tlo, thi, trunc, nflag);
-                joc = (oc == xo) ? j : (ok ? ssl_range(T, 0, n - 1, oc) : 0);
-                const double Goc = ok ? lerp_at(T, G, n, joc, oc) : 0.0;
-                double Gic = 0.0;
-                if (co_in_range(ic, tlo, thi, trunc, nflag)) {
-                    jic = (ic == tin) ? jtin : (ic == xo ? j : ssl_range(T, 0, n - 1, ic));
-                    Gic = lerp_at(T, G, n, jic, ic);
-                }
-                if (j + 1 >= n) {
-                    nflag |= trunc ? SBR_ENGINE_TRUNC : SBR_OOB;
-                    term = 3;
-                } else {
-                    const double eps = T[j + 1] - T[j];
-                    xoe = oc + eps; xie = ic + eps;
-                    oke = co_in_range(xoe, tlo, thi, trunc, nflag);
-                    oki = co_in_range(xie, tlo, thi, trunc, nflag);
-                    if (nflag) term = 3;
-                    else {
-                        AW = Goc - Gic;
-                        err = AW - kappa;
-                        if (fabs(err) <= tolerance) term = 4;
-                    }
-                }
-            }
-        }
-        int node = 1, stop = 0;
-        for (int lev = 0; lev < 6 && !stop; lev++) {
-            const int src = node - 1;
-            const int t_ = __builtin_amdgcn_readlane(term, src);
-            if (t_) {
-                stop = 1;
-                r.iters = t_ == 5 ? max_iters : iter0 + lev;
-                if (t_ == 1) s = SBR_NO_RUN_COLLAPSE;
-                else if (t_ == 2) s = SBR_NO_RUN_MAXITER;
-                else if (t_ == 3) flag |= (uint32_t)__builtin_amdgcn_readlane((int)nflag, src);
-                else if (t_ == 4) {
-                    const double xo_t = co_rl(xo, src), AW_t = co_rl(AW, src), err_t = co_rl(err, src);
-                    const double xoe_t = co_rl(xoe, src), xie_t = co_rl(xie, src);
-                    const int joc_t = __builtin_amdgcn_readlane(joc, src), jic_t = __builtin_amdgcn_readlane(jic, src);
-                    const bool oke_t = __builtin_amdgcn_readlane(oke ? 1 : 0, src) != 0;
-                    const bool oki_t = __builtin_amdgcn_readlane(oki ? 1 : 0, src) != 0;
-                    double Goce = 0.0, Gice = 0.0;
-                    if (oke_t) Goce = lerp_at(T, G, n, wave_ssl(T, joc_t, n - 1, xoe_t), xoe_t);
-                    if (oki_t) Gice = lerp_at(T, G, n, wave_ssl(T, jic_t, n - 1, xie_t), xie_t);
-                    const double AWe = Goce - Gice;
-                    if (AWe >= AW_t) { s = SBR_RUN; xi = xo_t; tolr = fabs(err_t); }
-                    else s = SBR_FALSE_EQ;
-                }
-                break;
-            }
-            const double e_ = co_rl(err, src);
-            const int j_ = __builtin_amdgcn_readlane(j, src);
-            if (e_ > 0) jhi = j_; else jlo = j_;
-            if (lev == 5) { // the next round's state: the child of this depth-5 node
-                const double xs = co_rl(xo, src), mn = co_rl(nmin, src), mxv = co_rl(nmax, src);
-                if (e_ > 0) { xmin = mn; xmax = xs; xnew = 0.5 * (xs + mn); }
-                else { xmin = xs; xmax = mxv; xnew = 0.5 * (xs + mxv); }
-            }
-            node = 2 * node + (e_ > 0 ? 0 : 1);
-        }
-        if (stop) break;
-        iter0 += 6;
-    }
-    } // default first iterate
-    if (flag) { r.status = flag | lbits; return; }
-    if (s != SBR_RUN) { r.status = s | lbits; return; }
-    // the AW stage's own range checks (solve_from_buffers: G(0), then the path's last τ̄ — the
-    // shifted arguments are nondecreasing, so the first failing knot fails there too)
-    if (!co_in_range(0.0, tlo, thi, trunc, flag)) { r.status = flag | lbits; return; }
-    const double icc = (tin >= xi) ? xi : tin;
-    const double occ = (tout > xi) ? xi : tout;
-    const double al = (tau(ntau - 1) - xi) + icc, bl = (tau(ntau - 1) - xi) + occ;
-    if (!((al > 0 ? al : 0.0) <= thi) || !((bl > 0 ? bl : 0.0) <= thi)) {
-        r.status = (trunc ? SBR_ENGINE_TRUNC : SBR_OOB) | lbits;
-        return;
-    }
-    r.xi = xi;
-    r.tol = tolr;
-    r.status = SBR_RUN | SBR_CONVERGED | lbits; // r.aw: the block's get_AW pass
-}
-
-// get_AW on τ̄ entries [i0, i1) with brackets slid along (eval_range's arithmetic); NaN-latching
-// max into mx (Julia maximum), paths written when given
-template <class P>
-__device__ __forceinline__ void co_eval(P T, P G, const int n, const int nle, const double ETA, const double xi,
-                                        const double icc, const double occ, const double G0, const int i0,
-                                        const int i1, double& mx, double* __restrict__ aw_cum,
-                                        double* __restrict__ aw_out, double* __restrict__ aw_in)
-{
-    if (i0 >= i1) return;
-    auto tau = [&](int i) -> double { return i < nle ? T[i] : ETA; };
-    auto x_of = [&](int i, double c) { const double v = (tau(i) - xi) + c; return v > 0 ? v : 0.0; };
-    int ka = ssl_range(T, 0, n - 1, x_of(i0, icc)), kb = ssl_range(T, 0, n - 1, x_of(i0, occ));
-    ka = ka < n - 2 ? ka : n - 2;
-    kb = kb < n - 2 ? kb : n - 2;
-    double ta0 = T[ka], ta1 = T[ka + 1], ga0 = G[ka], ga1 = G[ka + 1];
-    double tb0 = T[kb], tb1 = T[kb + 1], gb0 = G[kb], gb1 = G[kb + 1];
-    for (int i = i0; i < i1; i++) {
-        const double ti = tau(i);
-        const double av = (ti - xi) + icc;
-        const double bv = (ti - xi) + occ;
-        const double xa = av > 0 ? av : 0.0;
-        const double xb = bv > 0 ? bv : 0.0;
-        while (ka < n - 2 && ta1 <= xa) { ka++; ta0 = ta1; ga0 = ga1; ta1 = T[ka + 1]; ga1 = G[ka + 1]; }
-        while (kb < n - 2 && tb1 <= xb) { kb++; tb0 = tb1; gb0 = gb1; tb1 = T[kb + 1]; gb1 = G[kb + 1]; }
-        const double da = (xa - ta0) / (ta1 - ta0);
-        const double gi = ga0 * (1.0 - da) + ga1 * da;
-        double go;
-        if (xb == tb0) go = gb0 * 1.0 + gb1 * 0.0; // eval_range's δ = 0 form (the same value)
-        else { const double db = (xb - tb0) / (tb1 - tb0); go = gb0 * (1.0 - db) + gb1 * db; }
-        const double awin = av >= 0 ? gi : 0.0;
-        const double awout = bv >= 0 ? go : 0.0;
-        const double v = (awout - awin) + G0;
-        if (aw_cum) aw_cum[i] = v;
-        if (aw_out) aw_out[i] = awout;
-        if (aw_in) aw_in[i] = awin;
-        if (mx == mx && (v != v || v > mx)) mx = v;
-    }
-}
-
 __global__ __launch_bounds__(CO_BLOCK) void point_coop_kernel(LearnBufs L, const double* __restrict__ eta,
                                                               const double* __restrict__ t_end,
                                                               const double* __restrict__ u, EqArgs a, ResultSoA out)

@@ -134,6 +134,7 @@ struct sbr_ctx {
     std::vector<hipEvent_t> ev_hn;   // per equilibrium launch of a baseline batch: its hazards normalised
     int64_t n_grid = 0;
     int64_t bt_budget = 0; // baseline batch learning workspaces, bytes (0: 40 % of free + held HBM)
+    int64_t pt_budget = 0; // learning workspace of a list of models (sbr_solve_points), bytes (0: the same default)
     size_t ev_used = 0;
     struct TRec {
         int kind; // 0 learning (+ hazard), 1 equilibrium
@@ -752,6 +753,56 @@ int run_baseline(sbr_ctx* c, hipStream_t s, const double* beta, const double* et
     return SBR_OK;
 }
 
+// workspace bytes a point of a list counts for against the budget (sbr.h: sbr_set_points_workspace)
+size_t point_bytes(size_t cap) { return 4 * cap * sizeof(double) + 6 * sizeof(int32_t); }
+
+// A list of models (sbr_solve_points): n points, each with its own seven parameters, in chunks
+// of at most n_chunk points through learning slot 0, all in stream order on s — the learning
+// launch of a single sweep (one lane per point, truncated after η, no hazard), then one
+// points_kernel workgroup per point.  A chunk's learning starts after the previous chunk's
+// equilibria (they share the rows); no host synchronisation.  Timing records: kind 0 = the
+// learning launches, kind 1 = the points kernel.
+int run_points(sbr_ctx* c, hipStream_t s, const double* beta, const double* eta, const double* t_end, double x0,
+               const double* u, const double* p, const double* kappa, const double* lambda, int64_t n,
+               const sbr_opts& o, const sbr::ResultSoA& out)
+{
+    const size_t cap = (size_t)o.knot_capacity;
+    size_t freeb = 0, total = 0;
+    (void)hipMemGetInfo(&freeb, &total);
+    const size_t held = c->ws_beta[0] * batch_col_bytes(c->ws_cap[0]);
+    const double budget = c->pt_budget > 0 ? (double)c->pt_budget : 0.4 * (double)(freeb + held);
+    int64_t n_chunk = (int64_t)(budget / (double)point_bytes(cap));
+    if (n_chunk > 64) n_chunk &= ~(int64_t)63; // whole learning waves
+    n_chunk = std::max<int64_t>(1, std::min<int64_t>(n_chunk, n));
+    // a workspace that already holds enough rows of this capacity is used as it is
+    for (;;) {
+        const int rc = ensure_learn(c, (size_t)n_chunk, cap);
+        if (rc == SBR_OK) break;
+        free_learn(c, 0);
+        if (n_chunk == 1) return rc;
+        (void)hipGetLastError(); // the failed hipMalloc's error must not surface at the next launch check
+        n_chunk = (n_chunk + 1) / 2;
+    }
+    c->last_slot = 0;
+    c->last_off = 0;
+    c->rs_used = false;
+    const sbr::LearnBufs& L = c->LW[0];
+    for (int64_t c0 = 0; c0 < n; c0 += n_chunk) {
+        const int64_t nc = std::min<int64_t>(n_chunk, n - c0);
+        // p and λ are per point: the hazard runs in points_kernel, not in the learning launch
+        sbr::LearnArgs la{x0, o.ode_reltol, o.ode_abstol, 0.0, 0.0, o.ode_maxiters, (int32_t)nc, 1, 0};
+        hipEvent_t t0 = tstart(c, s);
+        HIP_TRY(c, sbr::launch_learn_kernel(beta + c0, eta + c0, t_end + c0, la, L, s, 1), SBR_EDEVICE);
+        tend(c, s, 0, t0);
+        const sbr::PointArgs pa{beta + c0, eta + c0,    t_end + c0,         u + c0,    p + c0,
+                                kappa + c0, lambda + c0, o.bisect_max_iters, c->lds_cap};
+        t0 = tstart(c, s);
+        HIP_TRY(c, sbr::launch_points(L, la, pa, result_rows(out, (size_t)c0), (int)nc, s), SBR_EDEVICE);
+        tend(c, s, 1, t0);
+    }
+    return SBR_OK;
+}
+
 int run_interest(sbr_ctx* c, hipStream_t s, const double* beta, const double* eta, const double* t_end, double x0,
                  const double* u, int64_t n_beta, int64_t n_u, double p, double kappa, double lambda, double r,
                  double delta, const sbr_opts& o, const sbr::ResultSoA& out, int64_t* steps, double* aw_path = nullptr,
@@ -792,6 +843,9 @@ int multi_sweep_interest(sbr_ctx* c, const double* beta, const double* eta, cons
 int multi_sweep_baseline(sbr_ctx* c, const double* beta, const double* eta, const double* t_end, double x0,
                          const double* u, int64_t n_beta, int64_t n_u, double p, double kappa, double lambda,
                          const sbr_opts& o, sbr_result_soa* out);
+int multi_solve_points(sbr_ctx* c, const double* beta, const double* eta, const double* t_end, double x0,
+                       const double* u, const double* p, const double* kappa, const double* lambda, int64_t n,
+                       const sbr_opts& o, sbr_result_soa* out);
 
 }  // namespace
 
@@ -1206,6 +1260,98 @@ int sbr_sweep_baseline(sbr_ctx* c, const double* beta, const double* eta, const 
         }
         return SBR_OK;
     });
+}
+
+// the checks sbr_solve_points and sbr_solve_points_dev share, before any array is looked at;
+// *done: nothing to do (n == 0)
+static int points_checks(sbr_ctx* c, const sbr_opts* opts, double x0, int64_t n, bool* done)
+{
+    *done = false;
+    if (guess_set(opts)) return fail(c, SBR_EARG, "xi_guess: only sbr_equilibrium_on_knots takes a first iterate");
+    if (!c) return SBR_EARG;
+    if (n < 0 || n > (1 << 30)) return fail(c, SBR_EARG, "list size");
+    if (!(x0 >= 0.0)) return fail(c, SBR_EARG, "ArgumentError: x0");
+    *done = n == 0;
+    return SBR_OK;
+}
+
+int sbr_solve_points_dev(sbr_ctx* c, void* stream, const double* beta, const double* eta, const double* t_end,
+                         double x0, const double* u, const double* p, const double* kappa, const double* lambda,
+                         int64_t n, const sbr_opts* opts, sbr_result_soa* out)
+{
+    bool done;
+    int rc = points_checks(c, opts, x0, n, &done);
+    if (rc) return rc;
+    SBR_SINGLE_DEVICE(c);
+    if (done) return SBR_OK;
+    if (!beta || !eta || !t_end || !u || !p || !kappa || !lambda || !out || !out->xi || !out->tau_in_unc ||
+        !out->tau_out_unc || !out->aw_max || !out->tol || !out->status)
+        return fail(c, SBR_EARG, "null array");
+    if (hipSetDevice(c->device) != hipSuccess) return fail(c, SBR_EDEVICE, "hipSetDevice");
+    const sbr_opts o = resolve(opts);
+    sbr::ResultSoA r{out->xi, out->tau_in_unc, out->tau_out_unc, out->aw_max, out->tol, out->status, out->iters};
+    return fenced(c, stream, true, [&](hipStream_t s) {
+        return run_points(c, s, beta, eta, t_end, x0, u, p, kappa, lambda, n, o, r);
+    });
+}
+
+int sbr_solve_points(sbr_ctx* c, const double* beta, const double* eta, const double* t_end, double x0,
+                     const double* u, const double* p, const double* kappa, const double* lambda, int64_t n,
+                     const sbr_opts* opts, sbr_result_soa* out)
+{
+    bool done;
+    int rc = points_checks(c, opts, x0, n, &done);
+    if (rc || done) return rc;
+    if (!beta || !eta || !t_end || !u || !p || !kappa || !lambda || !out) return fail(c, SBR_EARG, "null array");
+    // per-point ArgumentErrors are per-point results (SBR_ARG_INVALID), found on the device
+    if (c->multi) return multi_solve_points(c, beta, eta, t_end, x0, u, p, kappa, lambda, n, resolve(opts), out);
+    if (hipSetDevice(c->device) != hipSuccess) return fail(c, SBR_EDEVICE, "hipSetDevice");
+    const sbr_opts o = resolve(opts);
+    const size_t np = (size_t)n;
+    const size_t in_bytes = 7 * np * 8;
+    const size_t out_bytes = np * (5 * 8 + 4 + 4);
+    rc = ensure_stage(c, in_bytes + out_bytes + 256);
+    if (rc) return rc;
+    char* base = (char*)c->stage;
+    double* din = (double*)base;
+    double* dres = (double*)(base + ((in_bytes + 255) & ~(size_t)255));
+    sbr::ResultSoA r{dres, dres + np, dres + 2 * np, dres + 3 * np, dres + 4 * np, (uint32_t*)(dres + 5 * np),
+                     (int32_t*)((uint32_t*)(dres + 5 * np) + np)};
+    rc = ensure_res_pin(c, out_bytes);
+    if (rc) return rc;
+    return fenced(c, nullptr, false, [&](hipStream_t s) -> int {
+        const double* hin[7] = {beta, eta, t_end, u, p, kappa, lambda};
+        for (int k = 0; k < 7; k++)
+            HIP_TRY(c, hipMemcpyAsync(din + k * np, hin[k], np * 8, hipMemcpyHostToDevice, s), SBR_EDEVICE);
+        int rc2 = run_points(c, s, din, din + np, din + 2 * np, x0, din + 3 * np, din + 4 * np, din + 5 * np,
+                             din + 6 * np, n, o, r);
+        if (rc2) return rc2;
+        // one DMA copy of the contiguous result block into pinned memory, then the fields into
+        // the caller's arrays on several host threads (nothing is written before the sync succeeds)
+        const size_t blk = np * (5 * 8 + 4 + (out->iters ? 4 : 0));
+        HIP_TRY(c, hipMemcpyAsync(c->res_pin, dres, blk, hipMemcpyDeviceToHost, s), SBR_EDEVICE);
+        HIP_TRY(c, hipStreamSynchronize(s), SBR_EDEVICE);
+        const char* P = (const char*)c->res_pin;
+        std::vector<std::array<size_t, 3>> pieces;
+        double* hs[5] = {out->xi, out->tau_in_unc, out->tau_out_unc, out->aw_max, out->tol};
+        for (int k = 0; k < 5; k++)
+            if (hs[k]) pieces.push_back({(size_t)hs[k], (size_t)(P + (size_t)k * np * 8), np * 8});
+        if (out->status) pieces.push_back({(size_t)out->status, (size_t)(P + 5 * np * 8), np * 4});
+        if (out->iters) pieces.push_back({(size_t)out->iters, (size_t)(P + 5 * np * 8 + np * 4), np * 4});
+        sbr_host::parallel_copy(pieces);
+        return SBR_OK;
+    });
+}
+
+int sbr_set_points_workspace(sbr_ctx* c, int64_t bytes)
+{
+    if (!c || bytes < 0) return SBR_EARG;
+    if (c->multi) { // every rank's own budget
+        for (int r = 0; r < sbr_multi_impl::size(c->multi); r++) sbr_multi_impl::child(c->multi, r)->pt_budget = bytes;
+        return SBR_OK;
+    }
+    c->pt_budget = bytes;
+    return SBR_OK;
 }
 
 int sbr_sweep_interest_dev(sbr_ctx* c, void* stream, const double* beta, const double* eta, const double* t_end,
@@ -2781,6 +2927,34 @@ int multi_sweep_baseline(sbr_ctx* c, const double* beta, const double* eta, cons
     if (o.early_exit_nan_run > 0 && out->status && out->xi && out->aw_max && out->tol)
         sbr_apply_early_exit(n_beta, n_u, o.early_exit_nan_run, out);
     return SBR_OK;
+}
+
+// a list of models: point i to rank i mod N (the columns of an n × 1 grid), seven arrays each
+int multi_solve_points(sbr_ctx* c, const double* beta, const double* eta, const double* t_end, double x0,
+                       const double* u, const double* p, const double* kappa, const double* lambda, int64_t n,
+                       const sbr_opts& o, sbr_result_soa* out)
+{
+    const int N = sbr_multi_impl::size(c->multi);
+    const int64_t cmax = (n + N - 1) / N;
+    std::vector<FieldSpec> fs = {{out->xi, 8, 1},  {out->tau_in_unc, 8, 1}, {out->tau_out_unc, 8, 1},
+                                 {out->aw_max, 8, 1}, {out->tol, 8, 1},      {out->status, 4, 1},
+                                 {out->iters, 4, 1}};
+    const double* hin[7] = {beta, eta, t_end, u, p, kappa, lambda};
+    auto stage = [&](int r, int64_t nc, void* in, hipStream_t) -> int {
+        std::vector<double> h(7 * nc);
+        for (int k = 0; k < 7; k++) gather_cols(hin[k], 1, r, N, nc, h.data() + k * nc);
+        return stage_host(in, h);
+    };
+    auto run = [&](int, int64_t nc, sbr_ctx* kid, hipStream_t s, void* in, const std::vector<void*>& f) -> int {
+        const double* d = (const double*)in;
+        sbr_result_soa ro{(double*)f[0], (double*)f[1], (double*)f[2], (double*)f[3], (double*)f[4],
+                          (uint32_t*)f[5], (int32_t*)f[6]};
+        return sbr_solve_points_dev(kid, s, d, d + nc, d + 2 * nc, x0, d + 3 * nc, d + 4 * nc, d + 5 * nc, d + 6 * nc,
+                                    nc, &o, &ro);
+    };
+    int rc = sbr_multi_impl::run_sharded(c->multi, n, 1, fs, (size_t)(7 * cmax) * 8, stage, run,
+                                         (o.flags & SBR_FLAG_RCCL_GATHER) != 0);
+    return rc ? fail(c, rc, sbr_multi_impl::last_error(c->multi)) : SBR_OK;
 }
 
 int multi_sweep_interest(sbr_ctx* c, const double* beta, const double* eta, const double* t_end, double x0,

@@ -102,6 +102,14 @@ struct ResultSoA {
     int32_t* iters;
 };
 
+// A list of models (points_kernel): the per-point parameters of the chunk's points, entry j
+// belonging to row j of the learning buffers and to result j.
+struct PointArgs {
+    const double *beta, *eta, *t_end, *u, *p, *kappa, *lam;
+    int32_t max_iters; // compute_ξ's max_iters
+    int32_t lds_cap;   // knots staged in LDS per array (3 arrays: t, G, HR); larger points run from global memory
+};
+
 // Hetero learning output: t [n_col][cap], G [n_col][cap][K], hr/hrI [n_col][K][cap].
 struct HeteroBufs {
     double* t;
@@ -239,6 +247,11 @@ hipError_t launch_equilibrium(const LearnBufs& L, const double* eta, const doubl
 // = knots staged per array (3 arrays: t, G, HR); larger columns run from global memory.
 hipError_t launch_point_coop(const LearnBufs& L, const double* eta, const double* t_end, const double* u,
                              const EqArgs& a, const ResultSoA& out, hipStream_t s, int n_points = 1);
+// one workgroup per point j < n_points (sbr_solve_points): the hazard of row j of L with p[j], λ[j]
+// (la.p / la.lam are ignored), then the equilibrium and AW_max of (u[j], κ[j]) into result j.  The
+// knots of row j come from launch_learn_kernel (la.fuse_hazard = 0) over pa.beta / eta / t_end.
+hipError_t launch_points(const LearnBufs& L, const LearnArgs& la, const PointArgs& pa, const ResultSoA& out,
+                         int n_points, hipStream_t s);
 // hazard_rate (solver.jl:153-185) of n_beta columns whose knots, n_knots, n_le (#knots <= η) and
 // status are in L (the hazard stage of launch_learn_logistic on its own)
 hipError_t launch_hazard(const double* beta, const double* eta, const LearnArgs& a, const LearnBufs& L, int n_beta,

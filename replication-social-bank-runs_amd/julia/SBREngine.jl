@@ -19,6 +19,7 @@ const SBR_RUN = UInt32(0x0001)
 const SBR_CONVERGED = UInt32(0x0002)
 const SBR_SKIPPED_EARLY_EXIT = UInt32(0x0100)
 const SBR_OOB = UInt32(0x0080)
+const SBR_ARG_INVALID = UInt32(0x0400)
 const SBR_SOCIAL_NOT_CONVERGED = UInt32(0x1000)
 
 struct Opts            # sbr_opts
@@ -109,6 +110,38 @@ function solve_equilibrium_grid(ctx::Context, β_vals, u_vals; η = 15.0, tspan_
         check(ctx, rc)
     end
     return (max_AW_matrix = aw, ξ = xi, τ_bar_IN_UNC = tin, τ_bar_OUT_UNC = tout, status = st)
+end
+
+"""
+    solve_points(ctx, β, u; η, tspan_end, p, κ, λ, x0)
+
+A list of models in one call: point `i` is `solve_learning` + `solve_equilibrium_baseline` +
+`get_AW_functions!` for `ModelParameters(β[i], η[i], u[i], p[i], κ[i], λ[i]; tspan = (0, tspan_end[i]))`
+— a cross-section of banks, the draws of a calibration.  `β` and `u` are vectors of one length;
+the keywords are vectors of that length or scalars (broadcast).  Pass each model's resolved η and
+tspan (the copy-modify carry-over of model.jl:189-211 is the caller's).  Returns vectors
+`(AW_max, ξ, τ̄_IN, τ̄_OUT, tolerance, status)`; a point that breaks a parameter rule of model.jl
+has `status == SBR_ARG_INVALID` and NaN results, the others are untouched.
+"""
+function solve_points(ctx::Context, β, u; η = 15.0, tspan_end = 30.0, p = 0.5, κ = 0.6, λ = 0.01, x0 = 1e-4)
+    βv = collect(Float64, β); n = length(βv)
+    col(x) = x isa Number ? fill(Float64(x), n) : collect(Float64, x)
+    uv = col(u); ηv = col(η); tv = col(tspan_end); pv = col(p); κv = col(κ); λv = col(λ)
+    all(length(v) == n for v in (uv, ηv, tv, pv, κv, λv)) ||
+        throw(ArgumentError("solve_points: every per-point argument needs length(β) = $n entries"))
+    xi = Vector{Float64}(undef, n); tin = similar(xi); tout = similar(xi); aw = similar(xi); tol = similar(xi)
+    st = Vector{UInt32}(undef, n)
+    opts = Ref(Opts(; early_exit = 0))
+    GC.@preserve βv uv ηv tv pv κv λv xi tin tout aw tol st begin
+        soa = Ref(ResultSoA(pointer(xi), pointer(tin), pointer(tout), pointer(aw), pointer(tol), pointer(st),
+                            Ptr{Int32}(C_NULL)))
+        rc = ccall((:sbr_solve_points, libsbr), Cint,
+                   (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Float64, Ptr{Float64}, Ptr{Float64},
+                    Ptr{Float64}, Ptr{Float64}, Int64, Ref{Opts}, Ref{ResultSoA}),
+                   ctx.ptr, βv, ηv, tv, x0, uv, pv, κv, λv, n, opts, soa)
+        check(ctx, rc)
+    end
+    return (AW_max = aw, ξ = xi, τ_bar_IN_UNC = tin, τ_bar_OUT_UNC = tout, tolerance = tol, status = st)
 end
 
 """

@@ -16,6 +16,7 @@ from .engine import (  # noqa: F401
     SolvedModelHetero,
     SolvedModelInterest,
     get_AW_functions_interest,
+    points_from_models,
     social_plan,
     social_plan_lanes,
     solve_equilibrium_baseline,
@@ -25,6 +26,7 @@ from .engine import (  # noqa: F401
     solve_equilibrium_interest,
     solve_equilibrium_social_learning,
     solve_learning,
+    solve_models,
 )
 from .grids import BaselineGrid, HeteroGrid, fig4_grid, fig5_grid, hetero_config4, hetero_script_grid, julia_range  # noqa: F401,E501
 from .model import (  # noqa: F401

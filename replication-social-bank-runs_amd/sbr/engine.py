@@ -218,6 +218,54 @@ class Engine:
         (sbr_batch_wait): ship grid k while the rest of the batch is still being swept."""
         check(self._L.sbr_batch_wait(self._ctx, stream, int(k)), self._ctx, "sbr_batch_wait")
 
+    # ------------------------------------------------------------------ lists of models
+    def solve_points(self, beta, u, eta, t_end, p, kappa, lam, x0=1e-4, max_iters: int = 100,
+                     knot_capacity: int = 65536, with_iters: bool = True, exhaustive: bool = False,
+                     flags: int = 0, out: dict | None = None) -> dict:
+        """n independent models, point i with its own (β, η, t_end, u, p, κ, λ)[i], through learning
+        → HR → buffers → bisection → AW_max in one call (sbr_solve_points).  The seven arguments
+        broadcast against each other (scalars are repeated).  Returns (n,) arrays; a point that
+        breaks a parameter rule of model.jl has status SBR_ARG_INVALID and NaN results, the others
+        are untouched.  ``out``: the caller's result arrays as in ``sweep_baseline``."""
+        cols = np.broadcast_arrays(*[np.asarray(a, np.float64) for a in (beta, eta, t_end, u, p, kappa, lam)])
+        if cols[0].ndim > 1:
+            raise ArgumentError("solve_points takes scalars and one-dimensional arrays")
+        n = cols[0].size
+        b, e, t, uu, pp, kk, ll = [np.ascontiguousarray(c.reshape(n)) for c in cols]
+        if out is None:
+            out = {k: np.empty(n) for k in RESULT_FIELDS}
+            out["status"] = np.empty(n, np.uint32)
+            out["iters"] = np.empty(n, np.int32) if with_iters else None
+        else:
+            out = host_result_views(out, n)
+        soa = _lib.ResultSoA(*[_ptr(out[k]) for k in (*RESULT_FIELDS, "status", "iters")])
+        opts = _lib.default_opts(early_exit_nan_run=0, bisect_max_iters=max_iters, knot_capacity=knot_capacity,
+                                 flags=flags | (_lib.SBR_FLAG_EXHAUSTIVE if exhaustive else 0))
+        rc = self._L.sbr_solve_points(self._ctx, _ptr(b), _ptr(e), _ptr(t), x0, _ptr(uu), _ptr(pp), _ptr(kk),
+                                      _ptr(ll), n, ctypes.byref(opts), ctypes.byref(soa))
+        check(rc, self._ctx, "sbr_solve_points")
+        return dict(out)
+
+    def solve_points_dev(self, beta, u, eta, t_end, p, kappa, lam, x0, out: dict, stream: int | None = None,
+                         max_iters: int = 100, knot_capacity: int = 65536, flags: int = 0):
+        """Device-pointer variant on torch tensors (float64 cuda, n elements each) — enqueue only,
+        no host sync.  ``out`` holds preallocated tensors as for ``sweep_baseline_dev``."""
+        n = beta.numel()
+        soa = _lib.ResultSoA(*_out_ptrs(out, (*RESULT_FIELDS, "status", "iters"), n,
+                                        required=(*RESULT_FIELDS, "status")))
+        opts = _lib.default_opts(early_exit_nan_run=0, bisect_max_iters=max_iters, knot_capacity=knot_capacity,
+                                 flags=flags)
+        ins = [_dptr(a, name, _F64, n) for a, name in ((beta, "beta"), (eta, "eta"), (t_end, "t_end"), (u, "u"),
+                                                       (p, "p"), (kappa, "kappa"), (lam, "lam"))]
+        rc = self._L.sbr_solve_points_dev(self._ctx, stream, ins[0], ins[1], ins[2], x0, ins[3], ins[4], ins[5],
+                                          ins[6], n, ctypes.byref(opts), ctypes.byref(soa))
+        check(rc, self._ctx, "sbr_solve_points_dev")
+
+    def set_points_workspace(self, nbytes: int):
+        """Budget in bytes for the learning workspace of ``solve_points`` (0 = the default, 40 % of
+        free HBM); a list that needs more runs in chunks (sbr_set_points_workspace)."""
+        check(self._L.sbr_set_points_workspace(self._ctx, int(nbytes)), self._ctx, "sbr_set_points_workspace")
+
     def learn_baseline(self, beta, eta, t_end, x0=1e-4, stop_after_eta=False, cap=65536, tol=None):
         beta = np.ascontiguousarray(beta, np.float64)
         nb = len(beta)
@@ -702,6 +750,32 @@ def default_engine() -> Engine:
     if _default is None:
         _default = Engine()
     return _default
+
+
+def points_from_models(models) -> dict:
+    """The arguments of ``Engine.solve_points`` for a sequence of ``ModelParameters``: the seven
+    per-point arrays and the shared ``x0``.  η and tspan are each model's own, already resolved
+    values, so the copy-modify carry-over (model.jl:189-211) is whatever the caller built.
+    ArgumentError if the models' x0 differ (the call takes one) or a tspan does not start at 0."""
+    models = list(models)
+    if not all(isinstance(m, ModelParameters) for m in models):
+        raise ArgumentError("points_from_models takes ModelParameters")
+    x0s = {m.learning.x0 for m in models}
+    if len(x0s) > 1:
+        raise ArgumentError(f"the models of one call share x0, got {sorted(x0s)}")
+    if any(m.learning.tspan[0] != 0.0 for m in models):
+        raise ArgumentError("the engine integrates from t = 0 (every reference call site does)")
+    col = lambda f: np.array([f(m) for m in models], np.float64)  # noqa: E731
+    return dict(beta=col(lambda m: m.learning.beta), u=col(lambda m: m.economic.u),
+                eta=col(lambda m: m.economic.eta), t_end=col(lambda m: m.learning.tspan[1]),
+                p=col(lambda m: m.economic.p), kappa=col(lambda m: m.economic.kappa),
+                lam=col(lambda m: m.economic.lam), x0=x0s.pop() if x0s else 1e-4)
+
+
+def solve_models(models, engine: Engine | None = None) -> dict:
+    """solve_learning + solve_equilibrium_baseline + get_AW_functions!(r).AW_max for every model of
+    a sequence of ``ModelParameters`` in one engine call: (n,) result arrays."""
+    return (engine or default_engine()).solve_points(**points_from_models(models))
 
 
 def social_plan(n_pts: int, live: int, coop_max: int = -1, waves: int = -1) -> dict:

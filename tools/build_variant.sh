@@ -8,7 +8,7 @@ make -s all
 name=$1; defs=${2:-}
 mkdir -p build_var/$name lib_var/$name
 objs=""
-for f in sbr_baseline sbr_hetero sbr_social sbr_capi sbr_multi; do
+for f in sbr_baseline sbr_points sbr_hetero sbr_social sbr_capi sbr_multi; do
   if [ -n "$defs" ]; then
     /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -fno-fast-math \
       -fno-gpu-flush-denormals-to-zero -Wno-unused-function $defs -c -o build_var/$name/$f.o csrc/$f.hip &
