@@ -84,6 +84,10 @@ typedef struct {
 /* Diagnostics of the social sweep: per-phase shader-cycle sums, read with
  * sbr_social_prof_read (results unchanged). */
 #define SBR_FLAG_DIAG_SOCIAL_PROF 0x800
+/* Diagnostics of the baseline equilibrium kernels: the AW_max scan ignores the CDF's
+ * slope-monotone window (no early stop at the peak) and prunes with its bounds alone.  Same
+ * results; with SBR_FLAG_DIAG_COUNT_AW_BLOCKS it shows what the window saves. */
+#define SBR_FLAG_DIAG_NO_AW_WINDOW 0x1000
 
 typedef struct {
     double* xi;          /* SolvedModel.ξ                       */

@@ -663,7 +663,7 @@ __device__ __forceinline__ void solve_from_buffers(P T, P G, P H, const Summ& S,
             const int ic = predicted ? ssl_range(T, 0, (nle > 0 ? nle : 1) - 1, tstar < T[0] ? T[0] : tstar) : 0;
             if (scan) {
                 aw_scan(T, G, n, ntau, nle, ETA, xi, icc, occ, G0, S.dd, ic < ntau ? ic : ntau - 1, mx, nblk_eval,
-                        S.koff);
+                        S.koff, S.wlo, S.whi, S.wm);
             } else
             {
             int b8 = -1, w0 = 0, w1 = 0;
@@ -990,9 +990,11 @@ __device__ __forceinline__ void eq_column(const int b, const int j0, const int j
     __shared__ int s_ndec;                 // decreases of G between consecutive knots
     __shared__ unsigned long long s_maxdec; // largest decrease (bits of a nonnegative double)
     __shared__ double s_thalf;
+    __shared__ int s_wb;                   // last knot of the slope-monotone window (Summ::whi)
+    __shared__ unsigned long long s_dmax;  // largest |slope| of G (bits of a nonnegative double)
     // every shared flag is initialised before the first barrier: lanes >= nq set
     // s_nonmono right after it, so a later store by thread 0 could clear their flag
-    if (threadIdx.x == 0) { eq_next = 0; s_nonmono = 0; s_noscan = 0; s_near1 = 0; s_ndec = 0; s_maxdec = 0; s_thalf = NAN; }
+    if (threadIdx.x == 0) { eq_next = 0; s_nonmono = 0; s_noscan = 0; s_near1 = 0; s_ndec = 0; s_maxdec = 0; s_thalf = NAN; s_wb = 0x7fffffff; s_dmax = 0; }
     if (fits) {
         for (int i = threadIdx.x; i < n; i += BLOCK) { sT[i] = gT[i]; sG[i] = gG[i]; }
         if (INTEREST)
@@ -1067,6 +1069,45 @@ __device__ __forceinline__ void eq_column(const int b, const int j0, const int j
                 smc[g] = mn; // block min for now
             }
         }
+        // aw_scan's slope-monotone window: slopes d_k = (G[k+1] − G[k])/(t[k+1] − t[k]).  With inc(k) ⇔
+        // d_k > d_(k−1) and dec(k) ⇔ d_k < d_(k−1), both strict, and kc the first k without inc(k), the slopes
+        // rise over [0, kc) and fall from kc up to the first k that has neither inc nor dec or has
+        // inc(k) after a k − 1 without it (that k − 1 is >= kc, and the first inc after kc follows a
+        // k − 1 without inc): wb is the smallest such k, a local test, so one atomicMin finds it.
+        // A computed slope is within 3.01·u of the real one (two differences, a quotient; u = 2^-53), so
+        // a computed difference above 2^-50 = 8·u times the larger magnitude implies the same order in
+        // real arithmetic; slopes below 2^-900 (where the quotient may round as a subnormal), infinite
+        // or NaN end the window.  A wave takes 62 slopes per trip, one division per lane: lanes 0 and 1
+        // recompute the two slopes before them, and the neighbours' values come by shuffles.
+        {
+            auto rises = [](double lo, double hi) { // hi > lo in real arithmetic
+                const double m = fabs(lo) > fabs(hi) ? fabs(lo) : fabs(hi);
+                return m >= 0x1p-900 && m <= 1e300 && hi - lo > 0x1p-50 * m;
+            };
+            const int ln = threadIdx.x & 63;
+            for (int q = threadIdx.x >> 6; q * 62 < n - 1; q += BLOCK >> 6) {
+                const int k = q * 62 + ln - 2;
+                const bool valid = k >= 0 && k <= n - 2;
+                const double d = valid ? (sG[k + 1] - sG[k]) / (sT[k + 1] - sT[k]) : 0.0;
+                const double d1 = __shfl_up(d, 1, 64);
+                const bool inc = rises(d1, d), dec = rises(d, d1);
+                const bool incp = __shfl_up((int)inc, 1, 64) != 0;
+                const bool mine = valid && ln >= 2;
+                const bool fail = mine && k >= 1 && ((!inc && !dec) || (k >= 2 && inc && !incp));
+                double ad = mine ? fabs(d) : 0.0;
+                ad = ad <= 1e300 ? ad : (double)INFINITY; // NaN too
+#pragma unroll
+                for (int off = 1; off < 64; off <<= 1) {
+                    const double o = __shfl_xor(ad, off, 64);
+                    ad = o > ad ? o : ad;
+                }
+                const unsigned long long fm = __ballot(fail);
+                if (ln == 0) {
+                    if (fm) atomicMin(&s_wb, q * 62 + (int)__builtin_ctzll(fm) - 2);
+                    atomicMax(&s_dmax, (unsigned long long)sbr_dbits(ad));
+                }
+            }
+        }
         __syncthreads();
         // prefix max / suffix min over blocks (NaN-propagating), two waves at once
         if (threadIdx.x == 0) {
@@ -1136,11 +1177,33 @@ __device__ __forceinline__ void eq_column(const int b, const int j0, const int j
             }
         }
         __syncthreads();
-        const double dd = (double)s_ndec * sbr_bitsd(s_maxdec); // ≥ the largest drawdown
-        S = Summ{hmax, hmin, pmc, smc, s_nonmono == 0, s_thalf,
+        // (values every lane reads from LDS are the same in all of them: kept in scalar registers,
+        // not in lane registers that stay live across a point's solve)
+        auto uni = [](double x) {
+            const unsigned long long v = sbr_dbits(x);
+            const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v);
+            const unsigned hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
+            return sbr_bitsd(((unsigned long long)hi << 32) | lo);
+        };
+        const double dd = uni((double)s_ndec * sbr_bitsd(s_maxdec)); // ≥ the largest drawdown
+        S = Summ{hmax, hmin, pmc, smc, s_nonmono == 0, uni(s_thalf),
                  n >= 2 && !s_noscan && dd <= 1e-12 && sG[0] >= 0.0 && sG[n - 1] <= 2.0, dd,
                  s_nonmono == 0 || s_noscan != 0, s_near1 == 0 ? 1 : 2,
                  hpm, hpn, hsm, hsn, nbh_s};
+        // the window as times, and the scan's extra margin (aw_scan's comment derives both)
+        const double dmax = sbr_bitsd(s_dmax);
+        if (n >= 2 && dmax <= 1e300 && !(a.diag & 16)) {
+            const int wb = s_wb < n - 1 ? s_wb : n - 1;
+            const double e0 = fabs(sT[0]), e1 = fabs(sT[n - 1]);
+            const double span = (sT[wb] + 2.0 * (e0 > e1 ? e0 : e1)) * (1.0 + 0x1p-40);
+            const double du = 0x1p-52 * span;
+            const double wm = 0x1p-46 + dmax * (0x1p-50 * span);
+            if (wm <= 1e-9) { // a larger margin would rarely let the scan stop: no window
+                S.wlo = uni((sT[0] > 0.0 ? sT[0] : 0.0) + du);
+                S.whi = uni(sT[wb] - du);
+                S.wm = uni(wm);
+            }
+        }
     }
     // Points are handed out to waves 64 at a time from an LDS counter, so a
     // wave that drew cheap no-run points goes back for more instead of idling

@@ -480,7 +480,7 @@ int launch_eq(sbr_ctx* c, hipStream_t s, const sbr::LearnBufs& L, const double* 
               const sbr::ResultSoA& out, double* aw_path, int group = 1, bool timed = true)
 {
     sbr::EqArgs ea{kappa, (int32_t)n_u, o.bisect_max_iters, c->lds_cap_b, aw_path,
-                   (o.flags & SBR_FLAG_EXHAUSTIVE) ? 1 : 0, (o.flags >> 8) & 7};
+                   (o.flags & SBR_FLAG_EXHAUSTIVE) ? 1 : 0, (o.flags >> 8) & 0x17};
     ea.group = group;
     hipEvent_t t0 = timed ? tstart(c, s) : nullptr;
     if (aw_path && n_beta == 1 && n_u == 1) { // single point with its path: the whole workgroup on it
@@ -664,7 +664,7 @@ int run_baseline_ready(sbr_ctx* c, hipStream_t s, const double* beta, const doub
     HIP_TRY(c, sbr::launch_learn_logistic(beta, eta, t_end, la, c->LW[0], c->rs_learn), SBR_EDEVICE);
     tend(c, c->rs_learn, 0, t0);
     sbr::EqArgs ea{kappa, (int32_t)n_u, o.bisect_max_iters, c->lds_cap_b, nullptr,
-                   (o.flags & SBR_FLAG_EXHAUSTIVE) ? 1 : 0, (o.flags >> 8) & 7};
+                   (o.flags & SBR_FLAG_EXHAUSTIVE) ? 1 : 0, (o.flags >> 8) & 0x17};
     sbr::ReadyArgs ra{q, q + 4, q + 4 + n_beta, (int32_t)(n_beta * tiles), tiles, kReadyTileU, kReadySpin};
     hipEvent_t t1 = tstart(c, c->rs_eq);
     HIP_TRY(c, sbr::launch_eq_ready(c->LW[0], beta, eta, t_end, u, la, ea, ra, out, 0, c->rs_eq), SBR_EDEVICE);
@@ -734,7 +734,7 @@ int run_baseline(sbr_ctx* c, hipStream_t s, const double* beta, const double* et
         }
         HIP_TRY(c, hipEventRecord(c->ev_learned[k], ls), SBR_EDEVICE);
         sbr::EqArgs ea{kappa, (int32_t)n_u, o.bisect_max_iters, c->lds_cap_b, nullptr,
-                       (o.flags & SBR_FLAG_EXHAUSTIVE) ? 1 : 0, (o.flags >> 8) & 7};
+                       (o.flags & SBR_FLAG_EXHAUSTIVE) ? 1 : 0, (o.flags >> 8) & 0x17};
         HIP_TRY(c, sbr::launch_equilibrium(Lk, eta + c0, t_end + c0, u, ea, result_rows(out, (size_t)(c0 * n_u)),
                                            (int)nb, ls), SBR_EDEVICE);
         if (c->timing) {
@@ -817,7 +817,7 @@ int run_interest(sbr_ctx* c, hipStream_t s, const double* beta, const double* et
     HIP_TRY(c, sbr::launch_learn_logistic(beta, eta, t_end, la, c->LW[0], s), SBR_EDEVICE);
     tend(c, s, 0, t0);
     sbr::EqArgs ea{kappa, (int32_t)n_u, o.bisect_max_iters, c->lds_cap, aw_path,
-                   (o.flags & SBR_FLAG_EXHAUSTIVE) ? 1 : 0, (o.flags >> 8) & 7};
+                   (o.flags & SBR_FLAG_EXHAUSTIVE) ? 1 : 0, (o.flags >> 8) & 0x17};
     sbr::InterestArgs ia{r, delta, o.ode_reltol, o.ode_abstol, o.ode_maxiters, steps, v_path, v_count};
     t0 = tstart(c, s);
     HIP_TRY(c, sbr::launch_interest(c->LW[0], eta, t_end, u, ea, ia, out, (int)n_beta, s), SBR_EDEVICE);
@@ -1885,7 +1885,7 @@ int on_knots(sbr_ctx* c, const double* t, const double* G, const double* pdf, in
             const sbr::ResultSoA r{zd + 2, zd + 3, zd + 4, zd + 5, zd + 6, (uint32_t*)(zd + 7), (int32_t*)(zd + 7) + 1};
             double* zp = zd + 16;
             sbr::EqArgs ea{kappa, 1, o.bisect_max_iters, c->lds_cap, want_aw ? zp : nullptr,
-                           (o.flags & SBR_FLAG_EXHAUSTIVE) ? 1 : 0, (o.flags >> 8) & 7,
+                           (o.flags & SBR_FLAG_EXHAUSTIVE) ? 1 : 0, (o.flags >> 8) & 0x17,
                            want_aw ? zp + ntau : nullptr, want_aw ? zp + 2 * ntau : nullptr, 1, dres};
             if (o.flags & SBR_FLAG_XI_GUESS) ea.xi_guess = o.xi_guess;
             HIP_TRY(c, sbr::launch_point_coop(L, dsc + 1, zd, zd + 1, ea, r, s), SBR_EDEVICE);
@@ -1901,12 +1901,12 @@ int on_knots(sbr_ctx* c, const double* t, const double* G, const double* pdf, in
                 // first-iterate bisection; the sweep kernel carries no guess path, it would cost the
                 // sweeps registers)
                 sbr::EqArgs ea{kappa, 1, o.bisect_max_iters, c->lds_cap, nullptr,
-                               (o.flags & SBR_FLAG_EXHAUSTIVE) ? 1 : 0, (o.flags >> 8) & 7, nullptr, nullptr, 1};
+                               (o.flags & SBR_FLAG_EXHAUSTIVE) ? 1 : 0, (o.flags >> 8) & 0x17, nullptr, nullptr, 1};
                 ea.xi_guess = o.xi_guess;
                 HIP_TRY(c, sbr::launch_point_coop(L, dsc + 1, du, du + 1, ea, r, s, (int)nu), SBR_EDEVICE);
             } else {
                 sbr::EqArgs ea{kappa, (int32_t)n_u, o.bisect_max_iters, c->lds_cap_b, nullptr,
-                               (o.flags & SBR_FLAG_EXHAUSTIVE) ? 1 : 0, (o.flags >> 8) & 7, nullptr, nullptr, 1};
+                               (o.flags & SBR_FLAG_EXHAUSTIVE) ? 1 : 0, (o.flags >> 8) & 0x17, nullptr, nullptr, 1};
                 HIP_TRY(c, sbr::launch_equilibrium(L, dsc + 1, du, du + 1, ea, r, 1, s, n <= c->lds_cap_b ? 1 : 2),
                         SBR_EDEVICE);
             }

@@ -54,6 +54,12 @@ struct Summ {
     const double* hsm;
     const double* hsn;
     int nbh;
+    // aw_scan's slope-monotone window, as times: the knot-to-knot slopes of G rise strictly from
+    // knot 0 and then fall strictly up to knot wb, so AW_cum is quasi-concave in τ̄ while both its
+    // arguments lie in [wlo, whi] = [max(t[0], 0) + δ, t[wb] − δ] (δ: the rounding of a shifted
+    // argument); wm is what rounding can add to a comparison of two AW_cum values there.  Empty
+    // (wlo > whi) where no summaries are built: the scan then prunes with its bounds alone.
+    double wlo = INFINITY, whi = -INFINITY, wm = 0.0;
 };
 
 template <class P>
@@ -97,13 +103,40 @@ __device__ __forceinline__ int first_ge_down(F key, int hi, double x)
 // (A knot offset 0 for the AW_OUT bound inside [ξ/2, 2ξ], where b_i = t[i] exactly, halved the exact
 // evaluations and was slower: an exact evaluation costs about what a bounded trip costs,
 // profiles/experiments/r05_d_*)
+//
+// The slope-monotone window (Summ::wlo, whi, wm).  Over the window's knots the
+// slopes of the interpolant Ĝ rise and then fall, so for s_out = ξ − occ ≤ s_in = ξ − icc the function
+// F(τ) = Ĝ(τ − s_out) − Ĝ(τ − s_in) has F′ = slope(b) − slope(a) ≥ 0 while both arguments are in the
+// convex part, nonincreasing while a is in the convex and b in the concave part, and ≤ 0 once both
+// are in the concave part: F is quasi-concave on the τ interval whose arguments stay in the
+// window.  Hence, for evaluated knots c′ and i and any knot j beyond i on the side away from c′,
+// all three inside the window:  F(τ̄_i) < F(τ̄_c′)  ⇒  F(τ̄_j) ≤ F(τ̄_i).
+// The computed v_i differs from F(τ̄_i) + G(0) by at most E = E_arg + E_op:
+//   E_arg  the computed a_i = fl(fl(τ̄_i − ξ) + icc) is off by at most u·(|τ̄_i − ξ| + |a_i|) ≤ u·(2·t[wb] + |icc|)
+//          (u = 2^-53; |τ̄_i − ξ| ≤ |a_i| + |icc| and 0 ≤ a_i ≤ t[wb] inside the window), b_i alike with occ; icc, occ
+//          and ξ lie on the grid, so both are within δ = 2^-52·(t[wb] + 2·max|t|), and Ĝ moves by at most
+//          D·δ per argument, D the largest |slope| of the column: E_arg ≤ 2·D·δ.  The window's ends
+//          are moved inward by δ, so the exact arguments are inside it whenever the computed are.
+//   E_op   the two lerps (δ_a, 1 − δ_a, two products, a sum: ≤ 12·u·max|G| each, max|G| ≤ 2 + dd) and the two
+//          last operations (≤ 10·u): E_op ≤ 58·u·(1 + dd) < 2^-47.
+// With wm = 2^-46 + D·2^-50·(t[wb] + 2·max|t|) ≥ 2·E, the test  v_i < mx − (M + wm)  on computed values, mx
+// held by a knot c′ inside the window, gives F(τ̄_i) < F(τ̄_c′) and so v_j ≤ F(τ̄_j) + G(0) + E ≤ v_i + 2·E < mx for
+// every such j: none of them can raise the maximum, and they are dismissed unvisited.  The scan
+// goes on with its bounds from the first knot outside the window (LA / UB hold the last
+// exact AW_IN / AW_OUT, valid bounds as before).  a_i > 0 inside the window (wlo > 0), so AW_IN and AW_OUT
+// are the two lerps there.  M itself is not loosened: the bounds use it as before.
 template <class P>
 __device__ __forceinline__ void aw_scan(P T, P G, const int n, const int ntau, const int nle, const double ETA,
                                         const double xi, const double icc, const double occ, const double G0,
-                                        const double dd, const int c, double& mx, int& nev, const int koff = 2)
+                                        const double dd, const int c, double& mx, int& nev, const int koff = 2,
+                                        const double wlo = INFINITY, const double whi = -INFINITY,
+                                        const double wm = 0.0)
 {
     const double M = 1e-14 + 4.0 * dd;
+    const double Mw = M + wm;
+    const bool wuse = occ >= icc && wlo <= whi;
     auto tau = [&](int i) -> double { return i < nle ? T[i] : ETA; };
+    auto bv_of = [&](int i) -> double { return (tau(i) - xi) + occ; };
     auto av_of = [&](int i) -> double { return (tau(i) - xi) + icc; };
     // a(τ̄_i)'s bracket window: k = min(searchsortedlast(t, x), n − 2), its two knots (t, G)
     int ka;
@@ -139,12 +172,14 @@ __device__ __forceinline__ void aw_scan(P T, P G, const int n, const int ntau, c
         nev++;
         return (awout - awin) + G0;
     };
+    bool mxin; // the running maximum is held by a knot inside the window
     // knot c
     {
         const double av = av_of(c), xa = av > 0 ? av : 0.0;
         seek(c, xa);
         const double v = exact(c, av, xa);
         if (v > mx) mx = v;
+        mxin = wuse && av >= wlo && bv_of(c) <= whi;
     }
     const int kc = ka;
     const double ub_left = awout;
@@ -158,18 +193,39 @@ __device__ __forceinline__ void aw_scan(P T, P G, const int n, const int ntau, c
         LA = LA > lb ? LA : lb;
         const double V = (((mx - G0) + LA) - M) - dd; // G[k] <= V: every knot up to k is <= V + dd
         const int k2 = i + koff < n - 1 ? i + koff : n - 1;
+        int inext;
         if (G[k2] > V) {
             const double v = exact(i, av, xa);
-            if (v > mx) mx = v;
             LA = awin;
-            i++;
-            continue;
+            const double bv = (ti - xi) + occ;
+            bool drop = false;
+            if (v > mx) {
+                mx = v;
+                mxin = wuse && av >= wlo && bv <= whi;
+            } else {
+                drop = mxin && bv <= whi && v < mx - Mw;
+            }
+            if (!drop) {
+                i++;
+                continue;
+            }
+            // dropped inside the window (a_i >= a_c′ >= wlo): every further knot with b_j <= whi is
+            // below the maximum; go on from the first one outside
+            if (bv_of(ntau - 1) <= whi) break;
+            int lo = i;
+            inext = ntau - 1; // b_lo <= whi < b_inext
+            while (inext - lo > 1) {
+                const int mid = (lo + inext) >> 1;
+                if (bv_of(mid) <= whi) lo = mid;
+                else inext = mid;
+            }
+        } else {
+            // every knot j with G[min(j + 2, n − 1)] <= V is at or below mx: skip to the first other
+            const int kl = ssl_gallop(G, n, k2, V);
+            if (kl >= n - 1) break;
+            // G[kl + 1] > V: the first knot whose bound is not dismissed
+            inext = kl + 1 - koff;
         }
-        // every knot j with G[min(j + 2, n − 1)] <= V is at or below mx: skip to the first other
-        const int kl = ssl_gallop(G, n, k2, V);
-        if (kl >= n - 1) break;
-        // G[kl + 1] > V: the first knot whose bound is not dismissed
-        const int inext = kl + 1 - koff;
         const double an = av_of(inext);
         seek(ka + (inext - i), an > 0 ? an : 0.0);
         i = inext;
@@ -190,16 +246,31 @@ __device__ __forceinline__ void aw_scan(P T, P G, const int n, const int ntau, c
         const double av = (ti - xi) + icc, xa = av > 0 ? av : 0.0;
         bwd(xa);
         const double lb = av >= 0 ? ga0 : 0.0;
+        int ks;
+        double tk;
         if (!(lb >= Vp)) {
             const double v = exact(i, av, xa);
-            if (v > mx) mx = v;
             UB = UB < awout ? UB : awout;
-            i--;
-            continue;
+            bool drop = false;
+            if (v > mx) {
+                mx = v;
+                mxin = wuse && av >= wlo && (ti - xi) + occ <= whi;
+            } else {
+                drop = mxin && av >= wlo && v < mx - Mw;
+            }
+            if (!drop) {
+                i--;
+                continue;
+            }
+            // dropped inside the window (b_i <= b_c′ <= whi): every further knot with a_j >= wlo is
+            // below the maximum; go on from the first one outside
+            ks = ka;
+            tk = wlo;
+        } else {
+            // knots j <= i with a_j >= t[k*] (k* = first knot with G >= Vp) are pruned
+            ks = first_ge_down([&](int k) { return G[k]; }, ka, Vp);
+            tk = T[ks];
         }
-        // knots j <= i with a_j >= t[k*] (k* = first knot with G >= Vp) are pruned
-        const int ks = first_ge_down([&](int k) { return G[k]; }, ka, Vp);
-        const double tk = T[ks];
         const int j = first_ge_down(av_of, i, tk);
         if (j == 0) break;
         const int inext = j - 1;

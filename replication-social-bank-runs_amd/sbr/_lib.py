@@ -30,6 +30,7 @@ SBR_FLAG_DIAG_STOP_AFTER_BUFFER = 0x100
 SBR_FLAG_DIAG_STOP_AFTER_BISECT = 0x200
 SBR_FLAG_DIAG_COUNT_AW_BLOCKS = 0x400
 SBR_FLAG_DIAG_SOCIAL_PROF = 0x800
+SBR_FLAG_DIAG_NO_AW_WINDOW = 0x1000
 
 
 class SBRNativeError(RuntimeError):
