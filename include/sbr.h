@@ -40,6 +40,13 @@ extern "C" {
 
 typedef struct sbr_ctx sbr_ctx;
 
+/* ode_reltol, ode_abstol and ode_maxiters hold for each ODE solve of a call separately: the learning
+ * solve, the interest extension's value function (one solve per point, its own step count against
+ * ode_maxiters) and, in the social extension, the initial logistic solve and every forced iterate.
+ * A solve that ode_maxiters or knot_capacity cuts short ends its knot grid there: SBR_ODE_MAXITERS /
+ * SBR_KNOT_OVERFLOW on the column's points, and a lookup past the last knot is the reference's
+ * BoundsError (SBR_OOB).  With tolerances or a cap other than the defaults the sweeps integrate
+ * the learning solve to t_end (no stop after η), so these bits are the full solve's. */
 typedef struct {
     double ode_reltol;          /* learning.jl:43 reltol = eps() (0 = eps(): every zero field is the default) */
     double ode_abstol;          /* learning.jl:43 abstol = eps() (0 = eps()) */

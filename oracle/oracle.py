@@ -20,6 +20,7 @@ _D = ctypes.c_double
 _I64 = ctypes.c_int64
 _I32 = ctypes.c_int32
 _P = ctypes.c_void_p
+_ODE = [_D, _D, _I64]  # rtol, atol, ODE maxiters: the trailing arguments of every solving entry point
 
 
 def build(force: bool = False) -> Path:
@@ -45,8 +46,9 @@ def lib() -> ctypes.CDLL:
         L.sbro_equilibrium_paths.argtypes = [_P, _P, _I64, _D, _D, _D, _D, _D, _D, _D, _I32] + [_P] * 9
         L.sbro_equilibrium_paths_pdf.restype = None
         L.sbro_equilibrium_paths_pdf.argtypes = [_P, _P, _P, _I64, _D, _D, _D, _D, _D, _D, _I32] + [_P] * 9
-        L.sbro_sweep_baseline.restype = ctypes.c_int
-        L.sbro_sweep_baseline.argtypes = [_P, _P, _P, _D, _P, _I64, _I64, _D, _D, _D, _I32, _I32] + [_P] * 8
+        L.sbro_sweep_baseline_opt.restype = ctypes.c_int
+        L.sbro_sweep_baseline_opt.argtypes = ([_P, _P, _P, _D, _P, _I64, _I64, _D, _D, _D, _I32, _I32] + [_P] * 8
+                                           + _ODE)
         L.sbro_apply_early_exit.restype = None
         L.sbro_apply_early_exit.argtypes = [_I64, _I64, _I32, _P, _P, _P, _P]
         L.sbro_detmath.restype = None
@@ -149,7 +151,8 @@ def equilibrium_paths_pdf(t, G, pdf, eta, t_end, u, p, kappa, lam, max_iters=100
     return out
 
 
-def sweep_baseline(beta, eta, t_end, u, p, kappa, lam, x0=1e-4, max_iters=100, nthreads=0):
+def sweep_baseline(beta, eta, t_end, u, p, kappa, lam, x0=1e-4, max_iters=100, nthreads=0, rtol=EPS, atol=EPS,
+                   ode_maxiters=1_000_000):
     beta = np.ascontiguousarray(beta, np.float64)
     eta = np.ascontiguousarray(np.broadcast_to(eta, beta.shape), np.float64)
     t_end = np.ascontiguousarray(np.broadcast_to(t_end, beta.shape), np.float64)
@@ -159,10 +162,10 @@ def sweep_baseline(beta, eta, t_end, u, p, kappa, lam, x0=1e-4, max_iters=100, n
     o["status"] = np.empty(nb * nu, np.uint32)
     o["iters"] = np.empty(nb * nu, np.int32)
     nk = np.empty(nb, np.int64)
-    rc = lib().sbro_sweep_baseline(_ptr(beta), _ptr(eta), _ptr(t_end), x0, _ptr(u), nb, nu, p, kappa, lam,
+    rc = lib().sbro_sweep_baseline_opt(_ptr(beta), _ptr(eta), _ptr(t_end), x0, _ptr(u), nb, nu, p, kappa, lam,
                                    max_iters, nthreads, _ptr(o["xi"]), _ptr(o["tau_in_unc"]),
                                    _ptr(o["tau_out_unc"]), _ptr(o["aw_max"]), _ptr(o["tol"]), _ptr(o["status"]),
-                                   _ptr(o["iters"]), _ptr(nk))
+                                   _ptr(o["iters"]), _ptr(nk), rtol, atol, ode_maxiters)
     if rc != 0:
         raise RuntimeError("oracle sweep failed")
     out = {k: v.reshape(nb, nu) for k, v in o.items()}
@@ -200,13 +203,14 @@ def detmath(x, y):
 
 
 def _hetero_sigs(L):
-    L.sbro_sweep_hetero.restype = ctypes.c_int
-    L.sbro_sweep_hetero.argtypes = [_I32, _P, _P, _P, _P, _D, _P, _I64, _I64, _D, _D, _D, _I32, _D, _I32] + [_P] * 8
-    L.sbro_learn_hetero.restype = _I64
-    L.sbro_learn_hetero.argtypes = [_P, _P, _I32, _D, _D, _P, _P, _I64, _P]
+    L.sbro_sweep_hetero_opt.restype = ctypes.c_int
+    L.sbro_sweep_hetero_opt.argtypes = ([_I32, _P, _P, _P, _P, _D, _P, _I64, _I64, _D, _D, _D, _I32, _D, _I32]
+                                        + [_P] * 8 + _ODE)
+    L.sbro_learn_hetero_opt.restype = _I64
+    L.sbro_learn_hetero_opt.argtypes = [_P, _P, _I32, _D, _D, _P, _P, _I64, _P] + _ODE
 
 
-def learn_hetero(betas, dist, t_end, x0=1e-4, cap=1 << 16):
+def learn_hetero(betas, dist, t_end, x0=1e-4, cap=1 << 16, rtol=EPS, atol=EPS, ode_maxiters=1_000_000):
     L = lib()
     _hetero_sigs(L)
     betas = np.ascontiguousarray(betas, np.float64)
@@ -215,7 +219,8 @@ def learn_hetero(betas, dist, t_end, x0=1e-4, cap=1 << 16):
     t = np.empty(cap)
     G = np.empty(cap * K)
     stats = np.zeros(8, np.int64)
-    n = L.sbro_learn_hetero(_ptr(betas), _ptr(dist), K, t_end, x0, _ptr(t), _ptr(G), cap, _ptr(stats))
+    n = L.sbro_learn_hetero_opt(_ptr(betas), _ptr(dist), K, t_end, x0, _ptr(t), _ptr(G), cap, _ptr(stats), rtol, atol,
+                            ode_maxiters)
     if n < 0:
         raise RuntimeError("oracle hetero learning failed")
     return t[:n].copy(), G[: n * K].reshape(n, K).copy(), dict(naccept=int(stats[0]), nreject=int(stats[1]),
@@ -224,7 +229,8 @@ def learn_hetero(betas, dist, t_end, x0=1e-4, cap=1 << 16):
                                                                 nswitch=int(stats[5]), nstiff=int(stats[6]))
 
 
-def sweep_hetero(betas, dist, eta, t_end, u, p, kappa, lam, x0=1e-4, max_iters=500, tolerance=1e-12, nthreads=0):
+def sweep_hetero(betas, dist, eta, t_end, u, p, kappa, lam, x0=1e-4, max_iters=500, tolerance=1e-12, nthreads=0,
+                 rtol=EPS, atol=EPS, ode_maxiters=1_000_000):
     """betas: [n_col, K] group rates per column; eta/t_end per column."""
     L = lib()
     _hetero_sigs(L)
@@ -241,10 +247,10 @@ def sweep_hetero(betas, dist, eta, t_end, u, p, kappa, lam, x0=1e-4, max_iters=5
     o["tau_in_unc"] = np.empty(n_col * nu * K)
     o["tau_out_unc"] = np.empty(n_col * nu * K)
     nk = np.empty(n_col, np.int64)
-    rc = L.sbro_sweep_hetero(K, _ptr(betas), _ptr(dist), _ptr(eta), _ptr(t_end), x0, _ptr(u), n_col, nu, p, kappa, lam,
-                             max_iters, tolerance, nthreads, _ptr(o["xi"]), _ptr(o["aw_max"]), _ptr(o["tol"]),
-                             _ptr(o["status"]), _ptr(o["iters"]), _ptr(o["tau_in_unc"]), _ptr(o["tau_out_unc"]),
-                             _ptr(nk))
+    rc = L.sbro_sweep_hetero_opt(K, _ptr(betas), _ptr(dist), _ptr(eta), _ptr(t_end), x0, _ptr(u), n_col, nu, p, kappa,
+                                 lam, max_iters, tolerance, nthreads, _ptr(o["xi"]), _ptr(o["aw_max"]),
+                                 _ptr(o["tol"]), _ptr(o["status"]), _ptr(o["iters"]), _ptr(o["tau_in_unc"]),
+                                 _ptr(o["tau_out_unc"]), _ptr(nk), rtol, atol, ode_maxiters)
     if rc != 0:
         raise RuntimeError("oracle hetero sweep failed")
     out = {k: v.reshape(n_col, nu) for k, v in o.items() if k not in ("tau_in_unc", "tau_out_unc")}
@@ -255,13 +261,13 @@ def sweep_hetero(betas, dist, eta, t_end, u, p, kappa, lam, x0=1e-4, max_iters=5
 
 
 def _social_sigs(L):
-    L.sbro_sweep_social.restype = ctypes.c_int
-    L.sbro_sweep_social.argtypes = ([_P, _P, _D, _P, _I64, _I64, _D, _D, _D, _P, _I32, _D, _I32, _I32, _I32]
-                                    + [_P] * 9)
+    L.sbro_sweep_social_opt.restype = ctypes.c_int
+    L.sbro_sweep_social_opt.argtypes = ([_P, _P, _D, _P, _I64, _I64, _D, _D, _D, _P, _I32, _D, _I32, _I32, _I32]
+                                    + [_P] * 9 + _ODE)
 
 
 def sweep_social(beta, eta, u, p, kappa, lam, cmp, x0=1e-4, tol=1e-4, max_iter=500, bisect_max_iters=100,
-                 nthreads=0, stats=False):
+                 nthreads=0, stats=False, rtol=EPS, atol=EPS, ode_maxiters=1_000_000):
     """solve_equilibrium_social_learning (social_learning_solver.jl:63-263) over β columns × u.
     cmp: [n_beta, n_cmp] comparison grids (range(0, η_b, length=1000), :103)."""
     L = lib()
@@ -277,10 +283,10 @@ def sweep_social(beta, eta, u, p, kappa, lam, cmp, x0=1e-4, tol=1e-4, max_iter=5
     o["iters"] = np.empty(nb * nu, np.int32)
     o["fp_iters"] = np.empty(nb * nu, np.int32)
     st = np.zeros(nb * nu * 4, np.int64) if stats else None
-    rc = L.sbro_sweep_social(_ptr(beta), _ptr(eta), x0, _ptr(u), nb, nu, p, kappa, lam, _ptr(cmp), cmp.shape[1], tol,
-                             max_iter, bisect_max_iters, nthreads, _ptr(o["xi"]), _ptr(o["tau_in_unc"]),
-                             _ptr(o["tau_out_unc"]), _ptr(o["aw_max"]), _ptr(o["tol"]), _ptr(o["status"]),
-                             _ptr(o["iters"]), _ptr(o["fp_iters"]), _ptr(st))
+    rc = L.sbro_sweep_social_opt(_ptr(beta), _ptr(eta), x0, _ptr(u), nb, nu, p, kappa, lam, _ptr(cmp), cmp.shape[1],
+                                 tol, max_iter, bisect_max_iters, nthreads, _ptr(o["xi"]), _ptr(o["tau_in_unc"]),
+                                 _ptr(o["tau_out_unc"]), _ptr(o["aw_max"]), _ptr(o["tol"]), _ptr(o["status"]),
+                                 _ptr(o["iters"]), _ptr(o["fp_iters"]), _ptr(st), rtol, atol, ode_maxiters)
     if rc != 0:
         raise RuntimeError("oracle social sweep failed")
     out = {k: v.reshape(nb, nu) for k, v in o.items()}
@@ -290,22 +296,23 @@ def sweep_social(beta, eta, u, p, kappa, lam, cmp, x0=1e-4, tol=1e-4, max_iter=5
     return out
 
 
-def social_point(beta, eta, u, p, kappa, lam, cmp, x0=1e-4, tol=1e-4, max_iter=500, cap=1 << 18):
+def social_point(beta, eta, u, p, kappa, lam, cmp, x0=1e-4, tol=1e-4, max_iter=500, cap=1 << 18, rtol=EPS, atol=EPS,
+                 ode_maxiters=1_000_000):
     """One solve_equilibrium_social_learning point with the last iterate's
     learning knots (t, G), AW_{n-1} at those knots and HR grid τ̄ (to rebuild the plotted
     AW paths and the SolvedModel's learning_pdf / HR)."""
     L = lib()
-    L.sbro_social_point.restype = _I64
-    L.sbro_social_point.argtypes = [_D, _D, _D, _D, _D, _D, _D, _P, _I32, _D, _I32, _P, _P, _P, _P, _P, _P, _P, _I64,
-                                    _P]
+    L.sbro_social_point_opt.restype = _I64
+    L.sbro_social_point_opt.argtypes = [_D] * 7 + [_P, _I32, _D, _I32] + [_P] * 7 + [_I64, _P] + _ODE
     cmp = np.ascontiguousarray(cmp, np.float64)
     res = np.zeros(5)
     st = np.zeros(1, np.uint32)
     fi = np.zeros(1, np.int32)
     t, G, tau, awo = np.empty(cap), np.empty(cap), np.empty(cap), np.empty(cap)
     ntau = np.zeros(1, np.int64)
-    n = L.sbro_social_point(beta, eta, x0, u, p, kappa, lam, _ptr(cmp), len(cmp), tol, max_iter, _ptr(res), _ptr(st),
-                            _ptr(fi), _ptr(t), _ptr(G), _ptr(tau), _ptr(awo), cap, _ptr(ntau))
+    n = L.sbro_social_point_opt(beta, eta, x0, u, p, kappa, lam, _ptr(cmp), len(cmp), tol, max_iter, _ptr(res),
+                                _ptr(st), _ptr(fi), _ptr(t), _ptr(G), _ptr(tau), _ptr(awo), cap, _ptr(ntau), rtol,
+                                atol, ode_maxiters)
     if n < 0:
         raise RuntimeError(f"oracle social path buffer too small ({-n} needed)")
     k = int(ntau[0])
@@ -313,13 +320,15 @@ def social_point(beta, eta, u, p, kappa, lam, cmp, x0=1e-4, tol=1e-4, max_iter=5
                 fp_iters=int(fi[0]), t=t[:n].copy(), G=G[:n].copy(), hr_tau=tau[:k].copy(), aw_old=awo[:n].copy())
 
 
-def sweep_interest(beta, eta, t_end, u, p, kappa, lam, r, delta, x0=1e-4, max_iters=100, nthreads=0):
+def sweep_interest(beta, eta, t_end, u, p, kappa, lam, r, delta, x0=1e-4, max_iters=100, nthreads=0, rtol=EPS,
+                   atol=EPS, ode_maxiters=1_000_000):
     """solve_learning + solve_equilibrium_interest (interest_rate_solver.jl:51-150) +
     get_AW_functions_interest!(…).AW_max over β columns × u; rk_steps = value-function
     Tsit5 steps per point (0 when r = 0)."""
     L = lib()
-    L.sbro_sweep_interest.restype = ctypes.c_int
-    L.sbro_sweep_interest.argtypes = [_P, _P, _P, _D, _P, _I64, _I64, _D, _D, _D, _D, _D, _I32, _I32] + [_P] * 8
+    L.sbro_sweep_interest_opt.restype = ctypes.c_int
+    L.sbro_sweep_interest_opt.argtypes = ([_P, _P, _P, _D, _P, _I64, _I64, _D, _D, _D, _D, _D, _I32, _I32] + [_P] * 8
+                                       + _ODE)
     beta = np.ascontiguousarray(np.atleast_1d(beta), np.float64)
     nb = len(beta)
     eta = np.ascontiguousarray(np.broadcast_to(eta, (nb,)), np.float64)
@@ -330,27 +339,29 @@ def sweep_interest(beta, eta, t_end, u, p, kappa, lam, r, delta, x0=1e-4, max_it
     o["status"] = np.empty(nb * nu, np.uint32)
     o["iters"] = np.empty(nb * nu, np.int32)
     o["rk_steps"] = np.empty(nb * nu, np.int64)
-    rc = L.sbro_sweep_interest(_ptr(beta), _ptr(eta), _ptr(t_end), x0, _ptr(u), nb, nu, p, kappa, lam, r, delta,
+    rc = L.sbro_sweep_interest_opt(_ptr(beta), _ptr(eta), _ptr(t_end), x0, _ptr(u), nb, nu, p, kappa, lam, r, delta,
                                max_iters, nthreads, _ptr(o["xi"]), _ptr(o["tau_in_unc"]), _ptr(o["tau_out_unc"]),
                                _ptr(o["aw_max"]), _ptr(o["tol"]), _ptr(o["status"]), _ptr(o["iters"]),
-                               _ptr(o["rk_steps"]))
+                               _ptr(o["rk_steps"]), rtol, atol, ode_maxiters)
     if rc != 0:
         raise RuntimeError("oracle interest sweep failed")
     return {k: v.reshape(nb, nu) for k, v in o.items()}
 
 
-def interest_point(beta, eta, t_end, u, p, kappa, lam, r, delta, x0=1e-4, cap=1 << 16):
+def interest_point(beta, eta, t_end, u, p, kappa, lam, r, delta, x0=1e-4, cap=1 << 16, rtol=EPS, atol=EPS,
+                   ode_maxiters=1_000_000):
     """One interest-rate equilibrium with its HR grid τ̄, HR(τ̄) and the value function
     V(τ̄) saved on that grid (value_function_solver.jl:66-112, saveat = HR knots)."""
     L = lib()
-    L.sbro_interest_point.restype = _I64
-    L.sbro_interest_point.argtypes = [_D, _D, _D, _D, _D, _D, _D, _D, _D, _D, _P, _P, _P, _P, _P, _P, _I64, _P]
+    L.sbro_interest_point_opt.restype = _I64
+    L.sbro_interest_point_opt.argtypes = ([_D, _D, _D, _D, _D, _D, _D, _D, _D, _D, _P, _P, _P, _P, _P, _P, _I64, _P]
+                                       + _ODE)
     res = np.zeros(5)
     st = np.zeros(1, np.uint32)
     tau, hr, V, aw = np.empty(cap), np.empty(cap), np.empty(cap), np.empty(cap)
     nv = np.zeros(1, np.int64)
-    n = L.sbro_interest_point(beta, eta, t_end, x0, u, p, kappa, lam, r, delta, _ptr(res), _ptr(st), _ptr(tau),
-                              _ptr(hr), _ptr(V), _ptr(aw), cap, _ptr(nv))
+    n = L.sbro_interest_point_opt(beta, eta, t_end, x0, u, p, kappa, lam, r, delta, _ptr(res), _ptr(st), _ptr(tau),
+                              _ptr(hr), _ptr(V), _ptr(aw), cap, _ptr(nv), rtol, atol, ode_maxiters)
     if n < 0:
         raise RuntimeError(f"oracle interest path buffer too small ({-n} needed)")
     k = int(nv[0])
@@ -358,13 +369,14 @@ def interest_point(beta, eta, t_end, u, p, kappa, lam, r, delta, x0=1e-4, cap=1 
                 hr_tau=tau[:n].copy(), hr=hr[:n].copy(), V=V[:k].copy(), aw_cum=aw[:n].copy())
 
 
-def hetero_point_paths(betas, dist, eta, t_end, u, p, kappa, lam, x0=1e-4, cap=1 << 16):
+def hetero_point_paths(betas, dist, eta, t_end, u, p, kappa, lam, x0=1e-4, cap=1 << 16, rtol=EPS, atol=EPS,
+                       ode_maxiters=1_000_000):
     """One heterogeneity equilibrium with the learning knots t, G [n, K], the per-group
     buffers, AW_total on the knots (get_AW_functions_hetero!, heterogeneity_solver.jl:386) and
     get_AW_hetero's per-group curves aw_out / aw_in [K, n] (:335-362)."""
     L = lib()
-    L.sbro_hetero_point_paths.restype = _I64
-    L.sbro_hetero_point_paths.argtypes = [_I32, _P, _P, _D, _D, _D, _D, _D, _D, _D, _P, _P, _P, _P, _P, _P, _P, _P, _I64]
+    L.sbro_hetero_point_paths_opt.restype = _I64
+    L.sbro_hetero_point_paths_opt.argtypes = [_I32, _P, _P] + [_D] * 7 + [_P] * 8 + [_I64] + _ODE
     betas = np.ascontiguousarray(betas, np.float64)
     dist = np.ascontiguousarray(dist, np.float64)
     K = len(dist)
@@ -373,8 +385,9 @@ def hetero_point_paths(betas, dist, eta, t_end, u, p, kappa, lam, x0=1e-4, cap=1
     tin, tout = np.empty(K), np.empty(K)
     t, G, aw = np.empty(cap), np.empty(cap * K), np.empty(cap)
     awg = np.empty((2 * K, cap))
-    n = L.sbro_hetero_point_paths(K, _ptr(betas), _ptr(dist), eta, t_end, x0, u, p, kappa, lam, _ptr(res), _ptr(st),
-                                  _ptr(tin), _ptr(tout), _ptr(t), _ptr(G), _ptr(aw), _ptr(awg), cap)
+    n = L.sbro_hetero_point_paths_opt(K, _ptr(betas), _ptr(dist), eta, t_end, x0, u, p, kappa, lam, _ptr(res), _ptr(st),
+                                  _ptr(tin), _ptr(tout), _ptr(t), _ptr(G), _ptr(aw), _ptr(awg), cap, rtol, atol,
+                                  ode_maxiters)
     if n < 0:
         raise RuntimeError("oracle hetero point failed")
     return dict(xi=res[0], aw_max=res[1], tol=res[2], status=int(st[0]), tau_in_unc=tin, tau_out_unc=tout,

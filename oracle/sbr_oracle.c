@@ -208,6 +208,13 @@ static inline double interp_dx(const double* t, const double* v, int64_t stride,
 /* (solve! / loopheader! / loopfooter!, PIController, AutoSwitch),           */
 /* OrdinaryDiffEqTsit5 1.5.0 and OrdinaryDiffEqRosenbrock 1.18.1             */
 /* (Manifest.toml:1511-1515, 1679-1683, 1643-1647) — not vendored.           */
+/* Every solving entry point named *_opt (sweeps, points, hetero learning)   */
+/* ends with the arguments rtol, atol, ode_maxiters: they hold for each ODE  */
+/* solve of the call — the learning solve, the interest value function, the  */
+/* social extension's initial solve and every forced iterate — like the      */
+/* device's sbr_opts (include/sbr.h).  oracle.py defaults them to eps(),     */
+/* eps() and SBR_DEFAULT_ODE_MAXITERS.  Arguments, not a global: the sweeps  */
+/* are OpenMP-parallel and one loaded library serves a whole test session.   */
 /* ------------------------------------------------------------------------ */
 /* rhs(ctx, t, x[m], dx[m], &oob) */
 typedef void (*rhs_fn)(void* ctx, double t, const double* x, double* dx, int* oob);
@@ -870,10 +877,11 @@ void sbro_equilibrium(const double* t, const double* G, int64_t n, double beta, 
 /* Baseline β×u sweep (scripts/1_baseline.jl:224-267 without the early exit) */
 /* learning + hazard once per β column (u-independent), then every u.       */
 /* ------------------------------------------------------------------------ */
-int sbro_sweep_baseline(const double* beta, const double* eta, const double* t_end, double x0, const double* u,
-                        int64_t n_beta, int64_t n_u, double p, double kappa, double lambda, int32_t max_iters,
-                        int32_t nthreads, double* xi, double* tin, double* tout, double* aw_max, double* tol,
-                        uint32_t* status, int32_t* iters, int64_t* nknots)
+int sbro_sweep_baseline_opt(const double* beta, const double* eta, const double* t_end, double x0, const double* u,
+                            int64_t n_beta, int64_t n_u, double p, double kappa, double lambda, int32_t max_iters,
+                            int32_t nthreads, double* xi, double* tin, double* tout, double* aw_max, double* tol,
+                            uint32_t* status, int32_t* iters, int64_t* nknots, double rtol, double atol,
+                            int64_t ode_maxiters)
 {
     int err = 0;
 #ifdef _OPENMP
@@ -886,8 +894,10 @@ int sbro_sweep_baseline(const double* beta, const double* eta, const double* t_e
         ode_sys_t S;
         double x0v = x0;
         double bb = beta[b];
-        if (ode_solve(sys_logistic(&bb, &S), 1, 0.0, t_end[b], &x0v, 2.220446049250313e-16, 2.220446049250313e-16,
-                      SBR_DEFAULT_ODE_MAXITERS, &kn, &st)) { err |= 1; continue; }
+        if (ode_solve(sys_logistic(&bb, &S), 1, 0.0, t_end[b], &x0v, rtol, atol, ode_maxiters, &kn, &st)) {
+            err |= 1;
+            continue;
+        }
         if (nknots) nknots[b] = kn.n;
         int64_t n = kn.n;
         double* g = (double*)malloc((size_t)n * sizeof(double));
@@ -986,8 +996,9 @@ static void jac_hetero(void* ctx, double t, const double* I, double* J, double* 
     }
 }
 
-int64_t sbro_learn_hetero(const double* betas, const double* dist, int32_t K, double t1, double x0, double* t_out,
-                          double* G_out, int64_t cap, int64_t* stats)
+int64_t sbro_learn_hetero_opt(const double* betas, const double* dist, int32_t K, double t1, double x0, double* t_out,
+                              double* G_out, int64_t cap, int64_t* stats, double rtol, double atol,
+                              int64_t ode_maxiters)
 {
     knots_t kn = {0};
     ode_stats_t st;
@@ -995,8 +1006,7 @@ int64_t sbro_learn_hetero(const double* betas, const double* dist, int32_t K, do
     for (int k = 0; k < K; k++) x0v[k] = x0;
     hetero_ctx hc = {K, betas, dist};
     const ode_sys_t S = {rhs_hetero, K <= MAXJ ? jac_hetero : NULL, &hc};
-    const double e = 2.220446049250313e-16;
-    if (K < 1 || K > MAXK || ode_solve(&S, K, 0.0, t1, x0v, e, e, SBR_DEFAULT_ODE_MAXITERS, &kn, &st)) {
+    if (K < 1 || K > MAXK || ode_solve(&S, K, 0.0, t1, x0v, rtol, atol, ode_maxiters, &kn, &st)) {
         knots_free(&kn);
         return -1;
     }
@@ -1198,10 +1208,11 @@ static void hetero_column(int32_t K, const double* bk, const double* dist, const
     free(cum);
 }
 
-int sbro_sweep_hetero(int32_t K, const double* betas, const double* dist, const double* eta, const double* t_end,
-                      double x0, const double* u, int64_t n_col, int64_t n_u, double p, double kappa, double lambda,
-                      int32_t max_iters, double tolerance, int32_t nthreads, double* xi, double* aw_max, double* tol,
-                      uint32_t* status, int32_t* iters, double* tin_out, double* tout_out, int64_t* nknots)
+int sbro_sweep_hetero_opt(int32_t K, const double* betas, const double* dist, const double* eta, const double* t_end,
+                          double x0, const double* u, int64_t n_col, int64_t n_u, double p, double kappa, double lambda,
+                          int32_t max_iters, double tolerance, int32_t nthreads, double* xi, double* aw_max,
+                          double* tol, uint32_t* status, int32_t* iters, double* tin_out, double* tout_out,
+                          int64_t* nknots, double rtol, double atol, int64_t ode_maxiters)
 {
     int err = 0;
     if (K < 1 || K > MAXK) return -1;
@@ -1217,8 +1228,7 @@ int sbro_sweep_hetero(int32_t K, const double* betas, const double* dist, const 
         for (int k = 0; k < K; k++) x0v[k] = x0;
         hetero_ctx hc = {K, bk, dist};
         const ode_sys_t S = {rhs_hetero, K <= MAXJ ? jac_hetero : NULL, &hc};
-        const double e = 2.220446049250313e-16;
-        if (ode_solve(&S, K, 0.0, t_end[c], x0v, e, e, SBR_DEFAULT_ODE_MAXITERS, &kn, &st)) { err |= 1; continue; }
+        if (ode_solve(&S, K, 0.0, t_end[c], x0v, rtol, atol, ode_maxiters, &kn, &st)) { err |= 1; continue; }
         if (nknots) nknots[c] = kn.n;
         const int64_t o = c * n_u;
         hetero_column(K, bk, dist, kn.t, kn.x, kn.n, eta[c], t_end[c], u, n_u, p, kappa, lambda, max_iters, tolerance,
@@ -1287,9 +1297,9 @@ typedef struct {
 
 static void social_point(double beta, double eta, double x0, double u, double p, double kappa, double lambda,
                          const double* cmp, int32_t n_cmp, double tol, int32_t max_iter, int32_t bisect_max_iters,
-                         point_t* out, int32_t* fp_iters, int64_t* stats, social_paths_t* paths)
+                         double rtol, double atol, int64_t ode_maxiters, point_t* out, int32_t* fp_iters,
+                         int64_t* stats, social_paths_t* paths)
 {
-    const double e = 2.220446049250313e-16;
     memset(out, 0, sizeof(*out));
     out->xi = NAN; out->aw_max = NAN; out->tol = INFINITY; out->tin = out->tout = NAN;
     *fp_iters = 0;
@@ -1300,7 +1310,7 @@ static void social_point(double beta, double eta, double x0, double u, double p,
     ode_stats_t st;
     ode_sys_t S0;
     double x0v = x0, bb = beta;
-    if (ode_solve(sys_logistic(&bb, &S0), 1, 0.0, eta, &x0v, e, e, SBR_DEFAULT_ODE_MAXITERS, &old, &st)) {
+    if (ode_solve(sys_logistic(&bb, &S0), 1, 0.0, eta, &x0v, rtol, atol, ode_maxiters, &old, &st)) {
         out->status = SBR_ODE_FAILED; knots_free(&old); return;
     }
     ode_bits |= st.status & (SBR_ODE_MAXITERS | SBR_STIFF_SWITCH | SBR_ODE_FAILED | SBR_OOB);
@@ -1314,7 +1324,7 @@ static void social_point(double beta, double eta, double x0, double u, double p,
         social_ctx sc = {beta, old.t, old.x, old.n};
         const ode_sys_t S = {rhs_social, jac_social, &sc};
         x0v = x0;
-        if (ode_solve(&S, 1, 0.0, eta, &x0v, e, e, SBR_DEFAULT_ODE_MAXITERS, &kn, &st)) {
+        if (ode_solve(&S, 1, 0.0, eta, &x0v, rtol, atol, ode_maxiters, &kn, &st)) {
             out->status = SBR_ODE_FAILED; knots_free(&kn); break;
         }
         s_acc += st.naccept; s_rej += st.nreject;
@@ -1409,11 +1419,11 @@ static void social_point(double beta, double eta, double x0, double u, double p,
 
 /* Social sweep over β columns × u; column b has η = eta[b]; cmp is
  * [n_beta][n_cmp] (the caller's range(0, η_b, length = n_cmp)). */
-int sbro_sweep_social(const double* beta, const double* eta, double x0, const double* u, int64_t n_beta, int64_t n_u,
-                      double p, double kappa, double lambda, const double* cmp, int32_t n_cmp, double tol,
-                      int32_t max_iter, int32_t bisect_max_iters, int32_t nthreads, double* xi, double* tin,
-                      double* tout, double* aw_max, double* tl, uint32_t* status, int32_t* iters, int32_t* fp_iters,
-                      int64_t* stats)
+int sbro_sweep_social_opt(const double* beta, const double* eta, double x0, const double* u, int64_t n_beta,
+                          int64_t n_u, double p, double kappa, double lambda, const double* cmp, int32_t n_cmp,
+                          double tol, int32_t max_iter, int32_t bisect_max_iters, int32_t nthreads, double* xi,
+                          double* tin, double* tout, double* aw_max, double* tl, uint32_t* status, int32_t* iters,
+                          int32_t* fp_iters, int64_t* stats, double rtol, double atol, int64_t ode_maxiters)
 {
 #ifdef _OPENMP
     if (nthreads > 0) omp_set_num_threads(nthreads);
@@ -1424,7 +1434,7 @@ int sbro_sweep_social(const double* beta, const double* eta, double x0, const do
         point_t r;
         int32_t fi;
         social_point(beta[b], eta[b], x0, u[j], p, kappa, lambda, cmp + b * n_cmp, n_cmp, tol, max_iter,
-                     bisect_max_iters, &r, &fi, stats ? stats + 4 * o : NULL, NULL);
+                     bisect_max_iters, rtol, atol, ode_maxiters, &r, &fi, stats ? stats + 4 * o : NULL, NULL);
         xi[o] = r.xi; tin[o] = r.tin; tout[o] = r.tout; aw_max[o] = r.aw_max; tl[o] = r.tol;
         status[o] = r.status;
         if (iters) iters[o] = r.iters;
@@ -1436,14 +1446,16 @@ int sbro_sweep_social(const double* beta, const double* eta, double x0, const do
 /* single social point with the last iterate's paths (learning knots t/G and the
  * HR grid τ̄) for the figure checks; res = {ξ, τ̄_IN, τ̄_OUT, AW_max, tol}.
  * Returns the knot count (negative -needed if cap is too small). */
-int64_t sbro_social_point(double beta, double eta, double x0, double u, double p, double kappa, double lambda,
-                          const double* cmp, int32_t n_cmp, double tol, int32_t max_iter, double* res,
-                          uint32_t* status, int32_t* fp_iters, double* t_out, double* G_out, double* tau_out,
-                          double* awo_out, int64_t cap, int64_t* n_tau)
+int64_t sbro_social_point_opt(double beta, double eta, double x0, double u, double p, double kappa, double lambda,
+                              const double* cmp, int32_t n_cmp, double tol, int32_t max_iter, double* res,
+                              uint32_t* status, int32_t* fp_iters, double* t_out, double* G_out, double* tau_out,
+                              double* awo_out, int64_t cap, int64_t* n_tau, double rtol, double atol,
+                              int64_t ode_maxiters)
 {
     social_paths_t sp = {t_out, G_out, tau_out, awo_out, cap, 0, 0};
     point_t r;
-    social_point(beta, eta, x0, u, p, kappa, lambda, cmp, n_cmp, tol, max_iter, 100, &r, fp_iters, NULL, &sp);
+    social_point(beta, eta, x0, u, p, kappa, lambda, cmp, n_cmp, tol, max_iter, 100, rtol, atol, ode_maxiters, &r,
+                 fp_iters, NULL, &sp);
     res[0] = r.xi; res[1] = r.tin; res[2] = r.tout; res[3] = r.aw_max; res[4] = r.tol;
     *status = r.status;
     *n_tau = sp.n_tau;
@@ -1453,17 +1465,19 @@ int64_t sbro_social_point(double beta, double eta, double x0, double u, double p
 /* one hetero point with its paths (aggregate_withdrawals_hetero.pdf): res = {ξ, AW_max, tol};
  * learning knots t[n], G[n][K], per-group buffers, AW_total on the knots and (aw_groups, may be
  * NULL) AW_OUT_k / AW_IN_k at rows k / K + k of stride cap — NaN without a run */
-int64_t sbro_hetero_point_paths(int32_t K, const double* betas, const double* dist, double eta, double t_end,
-                                double x0, double u, double p, double kappa, double lambda, double* res,
-                                uint32_t* status, double* tin, double* tout, double* t_out, double* G_out,
-                                double* aw_out, double* aw_groups, int64_t cap)
+int64_t sbro_hetero_point_paths_opt(int32_t K, const double* betas, const double* dist, double eta, double t_end,
+                                    double x0, double u, double p, double kappa, double lambda, double* res,
+                                    uint32_t* status, double* tin, double* tout, double* t_out, double* G_out,
+                                    double* aw_out, double* aw_groups, int64_t cap, double rtol, double atol,
+                                    int64_t ode_maxiters)
 {
     int32_t it = 0;
     int64_t nk = 0;
-    if (sbro_sweep_hetero(K, betas, dist, &eta, &t_end, x0, &u, 1, 1, p, kappa, lambda, 500, 1e-12, 1, &res[0],
-                          &res[1], &res[2], status, &it, tin, tout, &nk))
+    if (sbro_sweep_hetero_opt(K, betas, dist, &eta, &t_end, x0, &u, 1, 1, p, kappa, lambda, 500, 1e-12, 1, &res[0],
+                          &res[1], &res[2], status, &it, tin, tout, &nk, rtol, atol, ode_maxiters))
         return -1;
-    const int64_t n = sbro_learn_hetero(betas, dist, K, t_end, x0, t_out, G_out, cap, NULL);
+    const int64_t n =
+        sbro_learn_hetero_opt(betas, dist, K, t_end, x0, t_out, G_out, cap, NULL, rtol, atol, ode_maxiters);
     if (n < 0) return n;
     if (*status & SBR_RUN) {
         int oob = 0;
@@ -1568,26 +1582,26 @@ static void saveat_step(void* ctx, double tprev, double t, double dt, const doub
     }
 }
 
-/* solve_value_function(hr, δ, r, u; tol = eps()) on the HR grid; returns the
+/* solve_value_function(hr, δ, r, u; tol) on the HR grid (the reference's tol = eps()); returns the
  * saved prefix length (== n unless the solve stopped early), V[0..) values */
-static int64_t value_function(const hazard_t* h, double delta, double r, double u, int64_t maxiters, double* V,
-                              ode_stats_t* st)
+static int64_t value_function(const hazard_t* h, double delta, double r, double u, double rtol, double atol,
+                              int64_t maxiters, double* V, ode_stats_t* st)
 {
     vf_ctx c = {h->tau, h->hr, h->n, delta, r, u};
     const double V0 = (u + delta) / (r + delta);
     saveat_t sv = {h->tau, h->n, 1, V};
     V[0] = V0; /* save_start: τ̄_1 = 0 = tspan[1] */
-    const double eps = 2.220446049250313e-16;
     const ode_sys_t S = {rhs_value, jac_value, &c};
-    ode_solve_cb(&S, 1, 0.0, h->tau[h->n - 1], &V0, eps, eps, maxiters, NULL, st, saveat_step, &sv);
+    ode_solve_cb(&S, 1, 0.0, h->tau[h->n - 1], &V0, rtol, atol, maxiters, NULL, st, saveat_step, &sv);
     return sv.next;
 }
 
 /* solve_equilibrium_interest (interest_rate_solver.jl:51-150) for one u given
  * the learning knots and the hazard; V_out (may be NULL) receives V on the grid */
 static void interest_point(const double* t, const double* G, int64_t n, const hazard_t* h, double t_end, double u,
-                           double kappa, double r, double delta, int32_t max_iters, point_t* res, double* V_out,
-                           int64_t* n_v, int64_t* steps, double* aw_path)
+                           double kappa, double r, double delta, int32_t max_iters, double rtol, double atol,
+                           int64_t ode_maxiters, point_t* res, double* V_out, int64_t* n_v, int64_t* steps,
+                           double* aw_path)
 {
     memset(res, 0, sizeof(*res));
     res->xi = NAN;
@@ -1601,7 +1615,7 @@ static void interest_point(const double* t, const double* G, int64_t n, const ha
         double* V = (double*)malloc((size_t)h->n * sizeof(double));
         double* hv = (double*)malloc((size_t)h->n * sizeof(double));
         ode_stats_t st;
-        const int64_t ns = value_function(h, delta, r, u, SBR_DEFAULT_ODE_MAXITERS, V, &st);
+        const int64_t ns = value_function(h, delta, r, u, rtol, atol, ode_maxiters, V, &st);
         bits = st.status & (SBR_ODE_MAXITERS | SBR_STIFF_SWITCH | SBR_ODE_FAILED | SBR_OOB);
         if (steps) *steps = st.naccept + st.nreject;
         if (n_v) *n_v = ns;
@@ -1642,10 +1656,11 @@ static void interest_point(const double* t, const double* G, int64_t n, const ha
 
 /* β × u sweep of the interest-rate equilibrium: learning + hazard per β
  * column (as the baseline), then the value function and equilibrium per u. */
-int sbro_sweep_interest(const double* beta, const double* eta, const double* t_end, double x0, const double* u,
-                        int64_t n_beta, int64_t n_u, double p, double kappa, double lambda, double r, double delta,
-                        int32_t max_iters, int32_t nthreads, double* xi, double* tin, double* tout, double* aw_max,
-                        double* tol, uint32_t* status, int32_t* iters, int64_t* steps)
+int sbro_sweep_interest_opt(const double* beta, const double* eta, const double* t_end, double x0, const double* u,
+                            int64_t n_beta, int64_t n_u, double p, double kappa, double lambda, double r, double delta,
+                            int32_t max_iters, int32_t nthreads, double* xi, double* tin, double* tout, double* aw_max,
+                            double* tol, uint32_t* status, int32_t* iters, int64_t* steps, double rtol, double atol,
+                            int64_t ode_maxiters)
 {
     int rc = 0;
 #ifdef _OPENMP
@@ -1653,12 +1668,11 @@ int sbro_sweep_interest(const double* beta, const double* eta, const double* t_e
 #pragma omp parallel for schedule(dynamic, 1) reduction(| : rc)
 #endif
     for (int64_t b = 0; b < n_beta; b++) {
-        const double eps = 2.220446049250313e-16;
         knots_t kn = {0};
         ode_stats_t st;
         ode_sys_t S;
         double bt = beta[b];
-        if (ode_solve(sys_logistic(&bt, &S), 1, 0.0, t_end[b], &x0, eps, eps, SBR_DEFAULT_ODE_MAXITERS, &kn, &st)) {
+        if (ode_solve(sys_logistic(&bt, &S), 1, 0.0, t_end[b], &x0, rtol, atol, ode_maxiters, &kn, &st)) {
             rc |= 1;
             continue;
         }
@@ -1671,8 +1685,8 @@ int sbro_sweep_interest(const double* beta, const double* eta, const double* t_e
             const int64_t o = b * n_u + j;
             point_t res;
             int64_t ns = 0;
-            interest_point(kn.t, kn.x, kn.n, &h, t_end[b], u[j], kappa, r, delta, max_iters, &res, NULL, NULL,
-                           steps ? &ns : NULL, NULL);
+            interest_point(kn.t, kn.x, kn.n, &h, t_end[b], u[j], kappa, r, delta, max_iters, rtol, atol, ode_maxiters,
+                           &res, NULL, NULL, steps ? &ns : NULL, NULL);
             xi[o] = res.xi; tin[o] = res.tin; tout[o] = res.tout; aw_max[o] = res.aw_max; tol[o] = res.tol;
             status[o] = res.status | lbits;
             if (iters) iters[o] = res.iters;
@@ -1687,15 +1701,15 @@ int sbro_sweep_interest(const double* beta, const double* eta, const double* t_e
 
 /* one point with its paths (figure parity): res[5] = ξ, τ̄_IN, τ̄_OUT, AW_max, tol;
  * hr_tau / hr_v / V (n_hr each, caller-sized ≥ the learning knot count + 1) */
-int64_t sbro_interest_point(double beta, double eta, double t_end, double x0, double u, double p, double kappa,
-                            double lambda, double r, double delta, double* res, uint32_t* status, double* hr_tau,
-                            double* hr_v, double* V, double* aw, int64_t cap, int64_t* n_v)
+int64_t sbro_interest_point_opt(double beta, double eta, double t_end, double x0, double u, double p, double kappa,
+                                double lambda, double r, double delta, double* res, uint32_t* status, double* hr_tau,
+                                double* hr_v, double* V, double* aw, int64_t cap, int64_t* n_v, double rtol,
+                                double atol, int64_t ode_maxiters)
 {
-    const double eps = 2.220446049250313e-16;
     knots_t kn = {0};
     ode_stats_t st;
     ode_sys_t S;
-    if (ode_solve(sys_logistic(&beta, &S), 1, 0.0, t_end, &x0, eps, eps, SBR_DEFAULT_ODE_MAXITERS, &kn, &st)) return -1;
+    if (ode_solve(sys_logistic(&beta, &S), 1, 0.0, t_end, &x0, rtol, atol, ode_maxiters, &kn, &st)) return -1;
     double* g = (double*)malloc((size_t)kn.n * sizeof(double));
     for (int64_t i = 0; i < kn.n; i++) g[i] = (beta * kn.x[i]) * (1.0 - kn.x[i]);
     hazard_t h;
@@ -1703,7 +1717,8 @@ int64_t sbro_interest_point(double beta, double eta, double t_end, double x0, do
     int64_t nh = h.n;
     if (nh > cap) { hazard_free(&h); free(g); knots_free(&kn); return -nh; }
     point_t pr;
-    interest_point(kn.t, kn.x, kn.n, &h, t_end, u, kappa, r, delta, 100, &pr, V, n_v, NULL, aw);
+    interest_point(kn.t, kn.x, kn.n, &h, t_end, u, kappa, r, delta, 100, rtol, atol, ode_maxiters, &pr, V, n_v, NULL,
+                   aw);
     if (aw && !(pr.status & SBR_RUN))
         for (int64_t i = 0; i < nh; i++) aw[i] = NAN;
     res[0] = pr.xi; res[1] = pr.tin; res[2] = pr.tout; res[3] = pr.aw_max; res[4] = pr.tol;
@@ -1714,4 +1729,88 @@ int64_t sbro_interest_point(double beta, double eta, double t_end, double x0, do
     free(g);
     knots_free(&kn);
     return nh;
+}
+
+/* ------------------------------------------------------------------------ */
+/* The entry points above under their earlier names and signatures, at the   */
+/* reference's integrator options (reltol = abstol = eps(), maxiters = 1e6): */
+/* a caller that binds them without the three trailing arguments gets what   */
+/* it always got.                                                            */
+/* ------------------------------------------------------------------------ */
+#define SBRO_EPS 2.220446049250313e-16
+
+int sbro_sweep_baseline(const double* beta, const double* eta, const double* t_end, double x0, const double* u,
+                        int64_t n_beta, int64_t n_u, double p, double kappa, double lambda, int32_t max_iters,
+                        int32_t nthreads, double* xi, double* tin, double* tout, double* aw_max, double* tol,
+                        uint32_t* status, int32_t* iters, int64_t* nknots)
+{
+    return sbro_sweep_baseline_opt(beta, eta, t_end, x0, u, n_beta, n_u, p, kappa, lambda, max_iters, nthreads, xi, tin,
+                                   tout, aw_max, tol, status, iters, nknots, SBRO_EPS, SBRO_EPS,
+                                   SBR_DEFAULT_ODE_MAXITERS);
+}
+
+int64_t sbro_learn_hetero(const double* betas, const double* dist, int32_t K, double t1, double x0, double* t_out,
+                          double* G_out, int64_t cap, int64_t* stats)
+{
+    return sbro_learn_hetero_opt(betas, dist, K, t1, x0, t_out, G_out, cap, stats, SBRO_EPS, SBRO_EPS,
+                                 SBR_DEFAULT_ODE_MAXITERS);
+}
+
+int sbro_sweep_hetero(int32_t K, const double* betas, const double* dist, const double* eta, const double* t_end,
+                      double x0, const double* u, int64_t n_col, int64_t n_u, double p, double kappa, double lambda,
+                      int32_t max_iters, double tolerance, int32_t nthreads, double* xi, double* aw_max, double* tol,
+                      uint32_t* status, int32_t* iters, double* tin_out, double* tout_out, int64_t* nknots)
+{
+    return sbro_sweep_hetero_opt(K, betas, dist, eta, t_end, x0, u, n_col, n_u, p, kappa, lambda, max_iters, tolerance,
+                                 nthreads, xi, aw_max, tol, status, iters, tin_out, tout_out, nknots, SBRO_EPS,
+                                 SBRO_EPS, SBR_DEFAULT_ODE_MAXITERS);
+}
+
+int64_t sbro_hetero_point_paths(int32_t K, const double* betas, const double* dist, double eta, double t_end,
+                                double x0, double u, double p, double kappa, double lambda, double* res,
+                                uint32_t* status, double* tin, double* tout, double* t_out, double* G_out,
+                                double* aw_out, double* aw_groups, int64_t cap)
+{
+    return sbro_hetero_point_paths_opt(K, betas, dist, eta, t_end, x0, u, p, kappa, lambda, res, status, tin, tout,
+                                       t_out, G_out, aw_out, aw_groups, cap, SBRO_EPS, SBRO_EPS,
+                                       SBR_DEFAULT_ODE_MAXITERS);
+}
+
+int sbro_sweep_social(const double* beta, const double* eta, double x0, const double* u, int64_t n_beta, int64_t n_u,
+                      double p, double kappa, double lambda, const double* cmp, int32_t n_cmp, double tol,
+                      int32_t max_iter, int32_t bisect_max_iters, int32_t nthreads, double* xi, double* tin,
+                      double* tout, double* aw_max, double* tl, uint32_t* status, int32_t* iters, int32_t* fp_iters,
+                      int64_t* stats)
+{
+    return sbro_sweep_social_opt(beta, eta, x0, u, n_beta, n_u, p, kappa, lambda, cmp, n_cmp, tol, max_iter,
+                                 bisect_max_iters, nthreads, xi, tin, tout, aw_max, tl, status, iters, fp_iters, stats,
+                                 SBRO_EPS, SBRO_EPS, SBR_DEFAULT_ODE_MAXITERS);
+}
+
+int64_t sbro_social_point(double beta, double eta, double x0, double u, double p, double kappa, double lambda,
+                          const double* cmp, int32_t n_cmp, double tol, int32_t max_iter, double* res,
+                          uint32_t* status, int32_t* fp_iters, double* t_out, double* G_out, double* tau_out,
+                          double* awo_out, int64_t cap, int64_t* n_tau)
+{
+    return sbro_social_point_opt(beta, eta, x0, u, p, kappa, lambda, cmp, n_cmp, tol, max_iter, res, status, fp_iters,
+                                 t_out, G_out, tau_out, awo_out, cap, n_tau, SBRO_EPS, SBRO_EPS,
+                                 SBR_DEFAULT_ODE_MAXITERS);
+}
+
+int sbro_sweep_interest(const double* beta, const double* eta, const double* t_end, double x0, const double* u,
+                        int64_t n_beta, int64_t n_u, double p, double kappa, double lambda, double r, double delta,
+                        int32_t max_iters, int32_t nthreads, double* xi, double* tin, double* tout, double* aw_max,
+                        double* tol, uint32_t* status, int32_t* iters, int64_t* steps)
+{
+    return sbro_sweep_interest_opt(beta, eta, t_end, x0, u, n_beta, n_u, p, kappa, lambda, r, delta, max_iters,
+                                   nthreads, xi, tin, tout, aw_max, tol, status, iters, steps, SBRO_EPS, SBRO_EPS,
+                                   SBR_DEFAULT_ODE_MAXITERS);
+}
+
+int64_t sbro_interest_point(double beta, double eta, double t_end, double x0, double u, double p, double kappa,
+                            double lambda, double r, double delta, double* res, uint32_t* status, double* hr_tau,
+                            double* hr_v, double* V, double* aw, int64_t cap, int64_t* n_v)
+{
+    return sbro_interest_point_opt(beta, eta, t_end, x0, u, p, kappa, lambda, r, delta, res, status, hr_tau, hr_v, V,
+                                   aw, cap, n_v, SBRO_EPS, SBRO_EPS, SBR_DEFAULT_ODE_MAXITERS);
 }

@@ -1214,7 +1214,7 @@ __device__ __forceinline__ void eq_column(const int b, const int j0, const int j
     const double ETA = eta[b], T1 = t_end[b];
     const uint32_t lbits = lst & (SBR_ODE_MAXITERS | SBR_STIFF_SWITCH | SBR_ODE_FAILED | SBR_KNOT_OVERFLOW);
     const bool bad_col = (lst & (SBR_ARG_INVALID | SBR_OOB)) || n < 2;
-    const bool trunc = !a.full_grid && n >= 2 && gT[n - 1] < T1;
+    const bool trunc = !a.full_grid && n >= 2 && gT[n - 1] < T1 && !(lst & kLearnCutBits);
     for (;;) {
         int base = 0;
         if (lane == 0) base = atomicAdd(&eq_next, 64);
@@ -1400,7 +1400,7 @@ __global__ __launch_bounds__(CO_BLOCK) void point_coop_kernel(LearnBufs L, const
     const double ETA = eta[0], T1 = t_end[0], uj = u[jb];
     const uint32_t lbits = lst & (SBR_ODE_MAXITERS | SBR_STIFF_SWITCH | SBR_ODE_FAILED | SBR_KNOT_OVERFLOW);
     const bool bad_col = (lst & (SBR_ARG_INVALID | SBR_OOB)) || n < 2;
-    const bool trunc = !a.full_grid && n >= 2 && L.t[n - 1] < T1;
+    const bool trunc = !a.full_grid && n >= 2 && L.t[n - 1] < T1 && !(lst & kLearnCutBits);
     if (threadIdx.x < 64) {
         PointResult r;
         if (bad_col || !(uj >= 0.0)) {

@@ -448,6 +448,25 @@ sbr_opts resolve(const sbr_opts* o)
     return r;
 }
 
+// Truncated learning (DESIGN.md §Truncated learning) stores a bit-exact prefix of the full solve,
+// but its status is the prefix's too: an SBR_ODE_MAXITERS or SBR_STIFF_SWITCH bit that the
+// reference's solve to t_end sets after the stop point would be lost.  With integrator options
+// of the caller's (a cap that the tail can reach, a tolerance at which Tsit5 hands over late) the
+// sweeps therefore integrate to t_end; the equilibrium stage reads the same knots either way.
+int32_t stop_after_eta(const sbr_opts& o)
+{
+    const double e = 2.220446049250313e-16;
+    return (o.ode_reltol == e && o.ode_abstol == e && o.ode_maxiters >= SBR_DEFAULT_ODE_MAXITERS) ? 1 : 0;
+}
+
+// The learning-only entry points return the learning solve's status (solve_learning has no
+// hazard): a column's status word also holds the hazard stage's SBR_OOB — no knot at η, as after a
+// solve that maxiters or the knot capacity cut short — which is no outcome of the learning solve.
+void strip_hazard_status(uint32_t* status, int64_t n)
+{
+    for (int64_t i = 0; status && i < n; i++) status[i] &= ~(uint32_t)SBR_OOB;
+}
+
 hipEvent_t next_event(sbr_ctx* c)
 {
     if (c->ev_used == c->ev_pool.size()) {
@@ -687,7 +706,7 @@ int run_baseline(sbr_ctx* c, hipStream_t s, const double* beta, const double* et
     if (rc) return rc;
     c->last_slot = 0;
     c->last_off = 0;
-    sbr::LearnArgs la{x0, o.ode_reltol, o.ode_abstol, p, lambda, o.ode_maxiters, (int32_t)n_beta, 1, 0};
+    sbr::LearnArgs la{x0, o.ode_reltol, o.ode_abstol, p, lambda, o.ode_maxiters, (int32_t)n_beta, stop_after_eta(o), 0};
     // per-column readiness on request (SBR_FLAG_READY_SWEEP): see above
     c->rs_used = !aw_path && n_beta >= 64 && (o.flags & SBR_FLAG_READY_SWEEP) &&
                  ensure_ready(c, (size_t)n_beta) == SBR_OK;
@@ -790,7 +809,7 @@ int run_points(sbr_ctx* c, hipStream_t s, const double* beta, const double* eta,
     for (int64_t c0 = 0; c0 < n; c0 += n_chunk) {
         const int64_t nc = std::min<int64_t>(n_chunk, n - c0);
         // p and λ are per point: the hazard runs in points_kernel, not in the learning launch
-        sbr::LearnArgs la{x0, o.ode_reltol, o.ode_abstol, 0.0, 0.0, o.ode_maxiters, (int32_t)nc, 1, 0};
+        sbr::LearnArgs la{x0, o.ode_reltol, o.ode_abstol, 0.0, 0.0, o.ode_maxiters, (int32_t)nc, stop_after_eta(o), 0};
         hipEvent_t t0 = tstart(c, s);
         HIP_TRY(c, sbr::launch_learn_kernel(beta + c0, eta + c0, t_end + c0, la, L, s, 1), SBR_EDEVICE);
         tend(c, s, 0, t0);
@@ -812,7 +831,7 @@ int run_interest(sbr_ctx* c, hipStream_t s, const double* beta, const double* et
     if (rc) return rc;
     c->last_slot = 0;
     c->last_off = 0;
-    sbr::LearnArgs la{x0, o.ode_reltol, o.ode_abstol, p, lambda, o.ode_maxiters, (int32_t)n_beta, 1, 0};
+    sbr::LearnArgs la{x0, o.ode_reltol, o.ode_abstol, p, lambda, o.ode_maxiters, (int32_t)n_beta, stop_after_eta(o), 0};
     hipEvent_t t0 = tstart(c, s);
     HIP_TRY(c, sbr::launch_learn_logistic(beta, eta, t_end, la, c->LW[0], s), SBR_EDEVICE);
     tend(c, s, 0, t0);
@@ -1084,7 +1103,8 @@ int sbr_sweep_baseline_batch_dev(sbr_ctx* c, void* stream, int64_t n_batch, cons
             // its rows leave through LDS as whole lines (mode 2).  Later groups run beside the
             // equilibrium launches and store directly (no LDS taken from the equilibrium slabs).
             const bool wide = m == 0;
-            sbr::LearnArgs la{x0, o.ode_reltol, o.ode_abstol, p, lambda, o.ode_maxiters, (int32_t)(gn * n_beta), 1, 1};
+            sbr::LearnArgs la{x0, o.ode_reltol, o.ode_abstol, p, lambda, o.ode_maxiters, (int32_t)(gn * n_beta),
+                              stop_after_eta(o), 1};
             hipEvent_t t0 = tstart(c, ls);
             // (a narrow first group — under 256 waves, e.g. a strong-scaled shard — stores directly:
             // the staging's flush instructions cost more than the stores' contention there)
@@ -1511,6 +1531,7 @@ int sbr_learn_baseline(sbr_ctx* c, const double* beta, const double* eta, const 
         if (n_knots) HIP_TRY(c, hipMemcpyAsync(n_knots, c->LW[0].n_knots, n_beta * 4, hipMemcpyDeviceToHost, s), SBR_EDEVICE);
         if (status) HIP_TRY(c, hipMemcpyAsync(status, c->LW[0].status, n_beta * 4, hipMemcpyDeviceToHost, s), SBR_EDEVICE);
         HIP_TRY(c, hipStreamSynchronize(s), SBR_EDEVICE);
+        strip_hazard_status(status, n_beta);
         return SBR_OK;
     });
 }
@@ -2141,6 +2162,7 @@ int sbr_learn_hetero(sbr_ctx* c, int32_t K, const double* betas, const double* d
         if (n_knots) HIP_TRY(c, hipMemcpyAsync(n_knots, c->H.n_knots, (size_t)n_col * 4, hipMemcpyDeviceToHost, s), SBR_EDEVICE);
         if (status) HIP_TRY(c, hipMemcpyAsync(status, c->H.status, (size_t)n_col * 4, hipMemcpyDeviceToHost, s), SBR_EDEVICE);
         HIP_TRY(c, hipStreamSynchronize(s), SBR_EDEVICE);
+        strip_hazard_status(status, n_col);
         return SBR_OK;
     });
 }

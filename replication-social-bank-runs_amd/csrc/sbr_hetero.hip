@@ -411,8 +411,9 @@ __global__ __launch_bounds__(64 * kHetLearnWG) void learn_hetero_wave_kernel(con
     int n_le = m;
     if (past) {
         n_le = m - 1;
-    } else if (!(st & SBR_KNOT_OVERFLOW)) {
-        // no knot beyond η: pdf(η) exists only if the last knot is η itself
+    } else {
+        // no knot beyond η — the solve ended there, or was cut short by maxiters, the knot capacity
+        // or a failed step: pdf(η) exists only if the last knot is η itself
         if (n >= 2 && tprev == ETA) {
             const double E = sbr_exp(lam * ETA);
             // bracket clamps to [n-2, n-1] with δ = 1: gprev*(1-1) ... = g_{n-1}

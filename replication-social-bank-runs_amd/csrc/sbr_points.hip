@@ -73,7 +73,7 @@ __global__ __launch_bounds__(CO_BLOCK) void points_kernel(LearnBufs L, LearnArgs
     const double* H = fits ? (const double*)sH : gH;
     const uint32_t lbits = lst & (SBR_ODE_MAXITERS | SBR_STIFF_SWITCH | SBR_ODE_FAILED | SBR_KNOT_OVERFLOW);
     const bool bad_col = (lst & (SBR_ARG_INVALID | SBR_OOB)) || n < 2;
-    const bool trunc = n >= 2 && gT[n - 1] < T1;
+    const bool trunc = n >= 2 && gT[n - 1] < T1 && !(lst & kLearnCutBits);
     if (threadIdx.x < 64) {
         PointResult r;
         if (bad_col) {

@@ -16,6 +16,12 @@ struct PointResult {
     int iters;
 };
 
+// Learning bits of a knot grid that ends early for a reason other than the engine's own stop after η
+// (DESIGN.md §Truncated learning): the integrator's iteration cap, the knot capacity, a failed step.
+// The reference's interpolant ends where such a grid ends, so a lookup past its last knot is the
+// BoundsError (SBR_OOB), never SBR_ENGINE_TRUNC.
+constexpr uint32_t kLearnCutBits = SBR_ODE_MAXITERS | SBR_KNOT_OVERFLOW | SBR_ODE_FAILED;
+
 // range check of an interpolation argument; returns false (and flags) when
 // Interpolations' Throw() extrapolation would raise.
 __device__ __forceinline__ bool in_range(double x, double tlo, double thi, bool trunc, uint32_t& flag)

@@ -46,6 +46,20 @@ def _ptr(a: np.ndarray | None):
 _F64, _I32, _I64 = "float64", "int32", "int64"
 
 
+def _opts(ode_rtol=None, ode_atol=None, ode_maxiters=None, **kw) -> _lib.Opts:
+    """sbr_default_opts with the fields ``kw`` set, and the integrator options that hold for every
+    ODE solve of the call (include/sbr.h, sbr_opts): ``ode_rtol`` → ode_reltol, ``ode_atol`` →
+    ode_abstol, ``ode_maxiters``.  None leaves a field 0: the reference's eps() / 1,000,000."""
+    o = _lib.default_opts(**kw)
+    if ode_rtol is not None:
+        o.ode_reltol = float(ode_rtol)
+    if ode_atol is not None:
+        o.ode_abstol = float(ode_atol)
+    if ode_maxiters is not None:
+        o.ode_maxiters = int(ode_maxiters)
+    return o
+
+
 def _dptr(t, name: str, kind: str, numel: int | None = None, optional: bool = False):
     """data_ptr() of a device tensor handed to a *_dev entry point, after the checks the
     kernels cannot make: a contiguous CUDA tensor of the right dtype holding at least
@@ -141,7 +155,8 @@ class Engine:
     # ------------------------------------------------------------------ sweeps
     def sweep_baseline(self, grid: BaselineGrid, early_exit: int = 0, max_iters: int = 100,
                        knot_capacity: int = 65536, with_iters: bool = True, exhaustive: bool = False,
-                       flags: int = 0, out: dict | None = None) -> dict:
+                       flags: int = 0, out: dict | None = None, ode_rtol: float | None = None,
+                       ode_atol: float | None = None, ode_maxiters: int | None = None) -> dict:
         """Every (β, u) of ``grid`` through learning → HR → buffers → bisection
         → AW_max.  Returns [n_beta, n_u] arrays (row i = β_i).  ``early_exit=5``
         applies the reference's 5-consecutive-no-run rule as a post-pass.  ``out``: the
@@ -156,9 +171,8 @@ class Engine:
         else:
             out = host_result_views(out, nb * nu)
         soa = _lib.ResultSoA(*[_ptr(out[k]) for k in (*RESULT_FIELDS, "status", "iters")])
-        opts = _lib.default_opts(early_exit_nan_run=early_exit, bisect_max_iters=max_iters,
-                                 knot_capacity=knot_capacity,
-                                 flags=flags | (_lib.SBR_FLAG_EXHAUSTIVE if exhaustive else 0))
+        opts = _opts(ode_rtol, ode_atol, ode_maxiters, early_exit_nan_run=early_exit, bisect_max_iters=max_iters,
+                     knot_capacity=knot_capacity, flags=flags | (_lib.SBR_FLAG_EXHAUSTIVE if exhaustive else 0))
         rc = self._L.sbr_sweep_baseline(self._ctx, _ptr(grid.beta), _ptr(grid.eta), _ptr(grid.t_end), grid.x0,
                                         _ptr(grid.u), nb, nu, grid.p, grid.kappa, grid.lam, ctypes.byref(opts),
                                         ctypes.byref(soa))
@@ -167,15 +181,16 @@ class Engine:
 
     def sweep_baseline_dev(self, beta, eta, t_end, u, p, kappa, lam, x0, out: dict, stream: int | None = None,
                            max_iters: int = 100, knot_capacity: int = 65536, exhaustive: bool = False,
-                           flags: int = 0):
+                           flags: int = 0, ode_rtol: float | None = None, ode_atol: float | None = None,
+                           ode_maxiters: int | None = None):
         """Device-pointer variant on torch tensors (float64 cuda) — no host sync.
         ``out`` holds preallocated tensors xi/tau_in_unc/tau_out_unc/aw_max/tol
         (float64), status (int32 viewed as uint32) and optional iters (int32)."""
         nb, nu = beta.numel(), u.numel()
         soa = _lib.ResultSoA(*_out_ptrs(out, (*RESULT_FIELDS, "status", "iters"), nb * nu,
                                         required=(*RESULT_FIELDS, "status")))
-        opts = _lib.default_opts(early_exit_nan_run=0, bisect_max_iters=max_iters, knot_capacity=knot_capacity,
-                                 flags=(_lib.SBR_FLAG_EXHAUSTIVE if exhaustive else 0) | flags)
+        opts = _opts(ode_rtol, ode_atol, ode_maxiters, early_exit_nan_run=0, bisect_max_iters=max_iters,
+                     knot_capacity=knot_capacity, flags=(_lib.SBR_FLAG_EXHAUSTIVE if exhaustive else 0) | flags)
         rc = self._L.sbr_sweep_baseline_dev(self._ctx, stream, _dptr(beta, "beta", _F64),
                                             _dptr(eta, "eta", _F64, nb), _dptr(t_end, "t_end", _F64, nb),
                                             x0, _dptr(u, "u", _F64), nb, nu, p, kappa, lam, ctypes.byref(opts),
@@ -183,7 +198,9 @@ class Engine:
         check(rc, self._ctx, "sbr_sweep_baseline_dev")
 
     def sweep_baseline_batch_dev(self, beta, eta, t_end, u, p, kappa, lam, x0, out: dict, stream: int | None = None,
-                                 max_iters: int = 100, knot_capacity: int = 65536, flags: int = 0):
+                                 max_iters: int = 100, knot_capacity: int = 65536, flags: int = 0,
+                                 ode_rtol: float | None = None, ode_atol: float | None = None,
+                                 ode_maxiters: int | None = None):
         """Pipelined sweep of several grids on torch tensors (float64 cuda):
         ``beta``/``eta``/``t_end`` are [n_batch, n_beta]; every ``out`` tensor
         is [n_batch, n_beta * n_u] (see sbr_sweep_baseline_batch_dev)."""
@@ -193,8 +210,8 @@ class Engine:
             raise ArgumentError("eta and t_end must be [n_batch, n_beta] like beta")
         soa = _lib.ResultSoA(*_out_ptrs(out, (*RESULT_FIELDS, "status", "iters"), nbat * nb * nu,
                                         required=(*RESULT_FIELDS, "status")))
-        opts = _lib.default_opts(early_exit_nan_run=0, bisect_max_iters=max_iters, knot_capacity=knot_capacity,
-                                 flags=flags)
+        opts = _opts(ode_rtol, ode_atol, ode_maxiters, early_exit_nan_run=0, bisect_max_iters=max_iters,
+                     knot_capacity=knot_capacity, flags=flags)
         rc = self._L.sbr_sweep_baseline_batch_dev(self._ctx, stream, nbat, _dptr(beta, "beta", _F64),
                                                   _dptr(eta, "eta", _F64), _dptr(t_end, "t_end", _F64), x0,
                                                   _dptr(u, "u", _F64), nb, nu, p, kappa, lam,
@@ -221,7 +238,8 @@ class Engine:
     # ------------------------------------------------------------------ lists of models
     def solve_points(self, beta, u, eta, t_end, p, kappa, lam, x0=1e-4, max_iters: int = 100,
                      knot_capacity: int = 65536, with_iters: bool = True, exhaustive: bool = False,
-                     flags: int = 0, out: dict | None = None) -> dict:
+                     flags: int = 0, out: dict | None = None, ode_rtol: float | None = None,
+                     ode_atol: float | None = None, ode_maxiters: int | None = None) -> dict:
         """n independent models, point i with its own (β, η, t_end, u, p, κ, λ)[i], through learning
         → HR → buffers → bisection → AW_max in one call (sbr_solve_points).  The seven arguments
         broadcast against each other (scalars are repeated).  Returns (n,) arrays; a point that
@@ -239,22 +257,24 @@ class Engine:
         else:
             out = host_result_views(out, n)
         soa = _lib.ResultSoA(*[_ptr(out[k]) for k in (*RESULT_FIELDS, "status", "iters")])
-        opts = _lib.default_opts(early_exit_nan_run=0, bisect_max_iters=max_iters, knot_capacity=knot_capacity,
-                                 flags=flags | (_lib.SBR_FLAG_EXHAUSTIVE if exhaustive else 0))
+        opts = _opts(ode_rtol, ode_atol, ode_maxiters, early_exit_nan_run=0, bisect_max_iters=max_iters,
+                     knot_capacity=knot_capacity, flags=flags | (_lib.SBR_FLAG_EXHAUSTIVE if exhaustive else 0))
         rc = self._L.sbr_solve_points(self._ctx, _ptr(b), _ptr(e), _ptr(t), x0, _ptr(uu), _ptr(pp), _ptr(kk),
                                       _ptr(ll), n, ctypes.byref(opts), ctypes.byref(soa))
         check(rc, self._ctx, "sbr_solve_points")
         return dict(out)
 
     def solve_points_dev(self, beta, u, eta, t_end, p, kappa, lam, x0, out: dict, stream: int | None = None,
-                         max_iters: int = 100, knot_capacity: int = 65536, flags: int = 0):
+                         max_iters: int = 100, knot_capacity: int = 65536, flags: int = 0,
+                         ode_rtol: float | None = None, ode_atol: float | None = None,
+                         ode_maxiters: int | None = None):
         """Device-pointer variant on torch tensors (float64 cuda, n elements each) — enqueue only,
         no host sync.  ``out`` holds preallocated tensors as for ``sweep_baseline_dev``."""
         n = beta.numel()
         soa = _lib.ResultSoA(*_out_ptrs(out, (*RESULT_FIELDS, "status", "iters"), n,
                                         required=(*RESULT_FIELDS, "status")))
-        opts = _lib.default_opts(early_exit_nan_run=0, bisect_max_iters=max_iters, knot_capacity=knot_capacity,
-                                 flags=flags)
+        opts = _opts(ode_rtol, ode_atol, ode_maxiters, early_exit_nan_run=0, bisect_max_iters=max_iters,
+                     knot_capacity=knot_capacity, flags=flags)
         ins = [_dptr(a, name, _F64, n) for a, name in ((beta, "beta"), (eta, "eta"), (t_end, "t_end"), (u, "u"),
                                                        (p, "p"), (kappa, "kappa"), (lam, "lam"))]
         rc = self._L.sbr_solve_points_dev(self._ctx, stream, ins[0], ins[1], ins[2], x0, ins[3], ins[4], ins[5],
@@ -266,7 +286,8 @@ class Engine:
         free HBM); a list that needs more runs in chunks (sbr_set_points_workspace)."""
         check(self._L.sbr_set_points_workspace(self._ctx, int(nbytes)), self._ctx, "sbr_set_points_workspace")
 
-    def learn_baseline(self, beta, eta, t_end, x0=1e-4, stop_after_eta=False, cap=65536, tol=None):
+    def learn_baseline(self, beta, eta, t_end, x0=1e-4, stop_after_eta=False, cap=65536, tol=None,
+                       ode_maxiters: int | None = None):
         beta = np.ascontiguousarray(beta, np.float64)
         nb = len(beta)
         eta = np.ascontiguousarray(np.broadcast_to(eta, beta.shape), np.float64)
@@ -275,22 +296,23 @@ class Engine:
         G = np.zeros((nb, cap))
         nk = np.zeros(nb, np.int32)
         st = np.zeros(nb, np.uint32)
-        opts = _lib.default_opts(knot_capacity=cap)
-        if tol is not None:  # solve_SIhomogeneous(…; tol): reltol = abstol = tol (learning.jl:41-51)
-            opts.ode_reltol = opts.ode_abstol = float(tol)
+        # solve_SIhomogeneous(…; tol): reltol = abstol = tol (learning.jl:41-51)
+        opts = _opts(tol, tol, ode_maxiters, knot_capacity=cap)
         rc = self._L.sbr_learn_baseline(self._ctx, _ptr(beta), _ptr(eta), _ptr(t_end), x0, nb, int(stop_after_eta),
                                         ctypes.byref(opts), _ptr(T), _ptr(G), cap, _ptr(nk), _ptr(st))
         check(rc, self._ctx, "sbr_learn_baseline")
         return [(T[i, : nk[i]].copy(), G[i, : nk[i]].copy(), int(st[i])) for i in range(nb)]
 
-    def solve_point_paths(self, beta, eta, t_end, u, p, kappa, lam, x0=1e-4, cap=65536):
+    def solve_point_paths(self, beta, eta, t_end, u, p, kappa, lam, x0=1e-4, cap=65536,
+                          ode_rtol: float | None = None, ode_atol: float | None = None,
+                          ode_maxiters: int | None = None):
         res = np.zeros(5)
         st = np.zeros(1, np.uint32)
         tau = np.zeros(cap)
         hr = np.zeros(cap)
         aw = np.zeros(cap)
         nt = np.zeros(1, np.int64)
-        opts = _lib.default_opts(knot_capacity=cap)
+        opts = _opts(ode_rtol, ode_atol, ode_maxiters, knot_capacity=cap)
         rc = self._L.sbr_solve_point_paths(self._ctx, beta, eta, t_end, x0, u, p, kappa, lam, ctypes.byref(opts),
                                            _ptr(res), _ptr(st), _ptr(tau), _ptr(hr), _ptr(aw), cap, _ptr(nt))
         check(rc, self._ctx, "sbr_solve_point_paths")
@@ -408,7 +430,8 @@ class Engine:
         return out
 
     def sweep_hetero(self, betas, dist, eta, t_end, u, p, kappa, lam, x0=1e-4, knot_capacity: int = 16384,
-                     with_groups: bool = True, exhaustive: bool = False) -> dict:
+                     with_groups: bool = True, exhaustive: bool = False, ode_rtol: float | None = None,
+                     ode_atol: float | None = None, ode_maxiters: int | None = None) -> dict:
         """Heterogeneity sweep: ``betas`` [n_col, K] group rates per column,
         ``eta``/``t_end`` per column, every u.  Returns [n_col, n_u] arrays and,
         with ``with_groups``, per-group buffers [n_col, n_u, K]."""
@@ -426,7 +449,8 @@ class Engine:
         tout = np.empty(n_col * nu * K) if with_groups else None
         soa = _lib.ResultSoA(_ptr(out["xi"]), None, None, _ptr(out["aw_max"]), _ptr(out["tol"]),
                              _ptr(out["status"]), _ptr(out["iters"]))
-        opts = _lib.default_opts(knot_capacity=knot_capacity, flags=_lib.SBR_FLAG_EXHAUSTIVE if exhaustive else 0)
+        opts = _opts(ode_rtol, ode_atol, ode_maxiters, knot_capacity=knot_capacity,
+                     flags=_lib.SBR_FLAG_EXHAUSTIVE if exhaustive else 0)
         rc = self._L.sbr_sweep_hetero(self._ctx, K, _ptr(betas), _ptr(dist), _ptr(eta), _ptr(t_end), x0, _ptr(u),
                                       n_col, nu, p, kappa, lam, ctypes.byref(opts), ctypes.byref(soa), _ptr(tin),
                                       _ptr(tout))
@@ -438,13 +462,15 @@ class Engine:
         return res
 
     def sweep_hetero_dev(self, K, betas, dist, eta, t_end, u, p, kappa, lam, x0, out: dict,
-                         stream: int | None = None, knot_capacity: int = 16384, flags: int = 0):
+                         stream: int | None = None, knot_capacity: int = 16384, flags: int = 0,
+                         ode_rtol: float | None = None, ode_atol: float | None = None,
+                         ode_maxiters: int | None = None):
         """Device-pointer hetero sweep on torch tensors (no host sync)."""
         n_col, nu = eta.numel(), u.numel()
         xi, aw, tl, st, it = _out_ptrs(out, ("xi", "aw_max", "tol", "status", "iters"), n_col * nu,
                                        required=("xi", "aw_max", "tol", "status"))
         soa = _lib.ResultSoA(xi, None, None, aw, tl, st, it)
-        opts = _lib.default_opts(knot_capacity=knot_capacity, flags=flags)
+        opts = _opts(ode_rtol, ode_atol, ode_maxiters, knot_capacity=knot_capacity, flags=flags)
         rc = self._L.sbr_sweep_hetero_dev(self._ctx, stream, K, _dptr(betas, "betas", _F64, n_col * K),
                                           _dptr(dist, "dist", _F64, K), _dptr(eta, "eta", _F64),
                                           _dptr(t_end, "t_end", _F64, n_col), x0, _dptr(u, "u", _F64), n_col, nu, p,
@@ -452,7 +478,9 @@ class Engine:
         check(rc, self._ctx, "sbr_sweep_hetero_dev")
 
     def sweep_hetero_batch_dev(self, K, betas, dist, eta, t_end, u, p, kappa, lam, x0, out: dict,
-                               stream: int | None = None, knot_capacity: int = 16384, flags: int = 0):
+                               stream: int | None = None, knot_capacity: int = 16384, flags: int = 0,
+                               ode_rtol: float | None = None, ode_atol: float | None = None,
+                               ode_maxiters: int | None = None):
         """Pipelined hetero sweep of several grids on torch tensors (see
         sbr_sweep_hetero_batch_dev): ``betas`` [n_batch, n_col, K], ``eta``/``t_end``
         [n_batch, n_col], every ``out`` tensor [n_batch, n_col * n_u]."""
@@ -463,7 +491,7 @@ class Engine:
         xi, aw, tl, st, it = _out_ptrs(out, ("xi", "aw_max", "tol", "status", "iters"), nbat * n_col * nu,
                                        required=("xi", "aw_max", "tol", "status"))
         soa = _lib.ResultSoA(xi, None, None, aw, tl, st, it)
-        opts = _lib.default_opts(knot_capacity=knot_capacity, flags=flags)
+        opts = _opts(ode_rtol, ode_atol, ode_maxiters, knot_capacity=knot_capacity, flags=flags)
         rc = self._L.sbr_sweep_hetero_batch_dev(self._ctx, stream, nbat, K, _dptr(betas, "betas", _F64),
                                                 _dptr(dist, "dist", _F64, K), _dptr(eta, "eta", _F64),
                                                 _dptr(t_end, "t_end", _F64), x0, _dptr(u, "u", _F64), n_col, nu, p,
@@ -471,7 +499,8 @@ class Engine:
         check(rc, self._ctx, "sbr_sweep_hetero_batch_dev")
 
     def sweep_social(self, beta, eta, u, p, kappa, lam, cmp=None, x0=1e-4, tol=1e-4, max_iter=500,
-                     knot_capacity: int = 0, workspace_bytes: int | None = None) -> dict:
+                     knot_capacity: int = 0, workspace_bytes: int | None = None, ode_rtol: float | None = None,
+                     ode_atol: float | None = None, ode_maxiters: int | None = None) -> dict:
         """Social-learning sweep (social_learning_solver.jl:63-263) over β columns × u.
         ``cmp`` [n_beta, n_cmp]: the comparison grids range(0, η_b, length=1000) (built
         with Julia's range semantics when omitted).  Returns [n_beta, n_u] arrays."""
@@ -491,7 +520,7 @@ class Engine:
         out["rk_steps"] = np.empty(nb * nu, np.int64)
         soa = _lib.ResultSoA(*[_ptr(out[k]) for k in ("xi", "tau_in_unc", "tau_out_unc", "aw_max", "tol", "status",
                                                       "iters")])
-        opts = _lib.default_opts(pad=knot_capacity)
+        opts = _opts(ode_rtol, ode_atol, ode_maxiters, pad=knot_capacity)
         if workspace_bytes is not None:
             check(self._L.sbr_set_social_workspace(self._ctx, int(workspace_bytes)), self._ctx,
                   "sbr_set_social_workspace")
@@ -502,12 +531,14 @@ class Engine:
         return {k: v.reshape(nb, nu) for k, v in out.items()}
 
     def sweep_social_dev(self, beta, eta, u, p, kappa, lam, cmp, x0, out: dict, tol=1e-4, max_iter=500,
-                         stream: int | None = None, knot_capacity: int = 0, flags: int = 0):
+                         stream: int | None = None, knot_capacity: int = 0, flags: int = 0,
+                         ode_rtol: float | None = None, ode_atol: float | None = None,
+                         ode_maxiters: int | None = None):
         """Device-pointer social sweep on torch tensors (enqueue only)."""
         nb, nu = beta.numel(), u.numel()
         soa = _lib.ResultSoA(*_out_ptrs(out, (*RESULT_FIELDS, "status", "iters"), nb * nu,
                                         required=(*RESULT_FIELDS, "status")))
-        opts = _lib.default_opts(pad=knot_capacity, flags=flags)
+        opts = _opts(ode_rtol, ode_atol, ode_maxiters, pad=knot_capacity, flags=flags)
         fp, rk = _out_ptrs(out, ("fp_iters", "rk_steps"), nb * nu)
         n_cmp = cmp.shape[-1]
         rc = self._L.sbr_sweep_social_dev(self._ctx, stream, _dptr(beta, "beta", _F64), _dptr(eta, "eta", _F64, nb),
@@ -517,7 +548,8 @@ class Engine:
         check(rc, self._ctx, "sbr_sweep_social_dev")
 
     def sweep_interest(self, beta, eta, t_end, u, p, kappa, lam, r, delta, x0=1e-4, max_iters: int = 100,
-                       knot_capacity: int = 65536) -> dict:
+                       knot_capacity: int = 65536, ode_rtol: float | None = None, ode_atol: float | None = None,
+                       ode_maxiters: int | None = None) -> dict:
         """Interest-rate extension over β columns × u (interest_rate_solver.jl:51-150 +
         get_AW_functions_interest!): the value function on the HR grid and buffers from
         h − rV (r > 0), the baseline for r = 0.  Returns [n_beta, n_u] arrays incl.
@@ -533,14 +565,16 @@ class Engine:
         out["iters"] = np.empty(nb * nu, np.int32)
         out["rk_steps"] = np.empty(nb * nu, np.int64)
         soa = _lib.ResultSoA(*[_ptr(out[k]) for k in (*RESULT_FIELDS, "status", "iters")])
-        opts = _lib.default_opts(early_exit_nan_run=0, bisect_max_iters=max_iters, knot_capacity=knot_capacity)
+        opts = _opts(ode_rtol, ode_atol, ode_maxiters, early_exit_nan_run=0, bisect_max_iters=max_iters,
+                     knot_capacity=knot_capacity)
         rc = self._L.sbr_sweep_interest(self._ctx, _ptr(beta), _ptr(eta), _ptr(t_end), x0, _ptr(u), nb, nu, p, kappa,
                                         lam, r, delta, ctypes.byref(opts), ctypes.byref(soa), _ptr(out["rk_steps"]))
         check(rc, self._ctx, "sbr_sweep_interest")
         return {k: v.reshape(nb, nu) for k, v in out.items()}
 
     def social_point_paths(self, beta, eta, u, p, kappa, lam, cmp=None, x0=1e-4, tol=1e-4, max_iter=500,
-                           cap=1 << 20) -> dict:
+                           cap=1 << 20, ode_rtol: float | None = None, ode_atol: float | None = None,
+                           ode_maxiters: int | None = None) -> dict:
         """One social-learning fixed point with the learning knots (t, G) of the returned
         SolvedModel and AW_{n-1} at those knots (the forcing of its learning_pdf,
         social_learning_dynamics.jl:98-114) — what scripts/4_social_learning.jl plots."""
@@ -552,7 +586,7 @@ class Engine:
         fp = np.zeros(1, np.int32)
         t, G, awo = np.empty(cap), np.empty(cap), np.empty(cap)
         nk = ctypes.c_int64()
-        opts = _lib.default_opts()
+        opts = _opts(ode_rtol, ode_atol, ode_maxiters)
         rc = self._L.sbr_social_point_paths(self._ctx, beta, eta, x0, u, p, kappa, lam, _ptr(cmp), len(cmp), tol,
                                             max_iter, ctypes.byref(opts), _ptr(res), _ptr(st), _ptr(fp), _ptr(t),
                                             _ptr(G), _ptr(awo), cap, ctypes.byref(nk))
@@ -561,7 +595,8 @@ class Engine:
         return dict(xi=res[0], tau_in_unc=res[1], tau_out_unc=res[2], aw_max=res[3], tol=res[4], status=int(st[0]),
                     fp_iters=int(fp[0]), t=t[:n].copy(), G=G[:n].copy(), aw_old=awo[:n].copy())
 
-    def learn_hetero(self, betas, dist, t_end, x0=1e-4, cap=16384) -> dict:
+    def learn_hetero(self, betas, dist, t_end, x0=1e-4, cap=16384, ode_rtol: float | None = None,
+                     ode_atol: float | None = None, ode_maxiters: int | None = None) -> dict:
         """solve_SInetwork_hetero (heterogeneity_learning.jl:49-94) for n_col columns: the shared
         knot grid t [n_col, cap] and group CDFs G [n_col, cap, K] (row c valid to n_knots[c])."""
         dist = np.ascontiguousarray(dist, np.float64)
@@ -572,13 +607,15 @@ class Engine:
         t_end = np.ascontiguousarray(np.broadcast_to(t_end, (nc,)), np.float64)
         t, G = np.empty((nc, cap)), np.empty((nc, cap, K))
         nk, st = np.zeros(nc, np.int32), np.zeros(nc, np.uint32)
-        opts = _lib.default_opts(early_exit_nan_run=0, knot_capacity=cap)
+        opts = _opts(ode_rtol, ode_atol, ode_maxiters, early_exit_nan_run=0, knot_capacity=cap)
         rc = self._L.sbr_learn_hetero(self._ctx, K, _ptr(betas), _ptr(dist), _ptr(t_end), x0, nc, ctypes.byref(opts),
                                       _ptr(t), _ptr(G), cap, _ptr(nk), _ptr(st))
         check(rc, self._ctx, "sbr_learn_hetero")
         return dict(t=t, G=G, n_knots=nk, status=st)
 
-    def hetero_point_paths(self, betas, dist, eta, t_end, u, p, kappa, lam, x0=1e-4, cap=65536) -> dict:
+    def hetero_point_paths(self, betas, dist, eta, t_end, u, p, kappa, lam, x0=1e-4, cap=65536,
+                           ode_rtol: float | None = None, ode_atol: float | None = None,
+                           ode_maxiters: int | None = None) -> dict:
         """One heterogeneity equilibrium with learning knots t, group CDFs G [n, K], the
         per-group buffers, AW_total(t) and the per-group AW_OUT_k / AW_IN_k curves on the knots
         (aw_out / aw_in [K, n]) — what scripts/2_heterogeneity.jl plots."""
@@ -591,7 +628,7 @@ class Engine:
         t, G, aw = np.empty(cap), np.empty(cap * K), np.empty(cap)
         awg = np.empty((2 * K, cap))
         nk = ctypes.c_int64()
-        opts = _lib.default_opts(early_exit_nan_run=0, knot_capacity=16384)
+        opts = _opts(ode_rtol, ode_atol, ode_maxiters, early_exit_nan_run=0, knot_capacity=16384)
         rc = self._L.sbr_hetero_point_paths(self._ctx, K, _ptr(betas), _ptr(dist), eta, t_end, x0, u, p, kappa, lam,
                                             ctypes.byref(opts), _ptr(res), _ptr(st), _ptr(tin), _ptr(tout), _ptr(t),
                                             _ptr(G), _ptr(aw), _ptr(awg), cap, ctypes.byref(nk))
@@ -601,14 +638,16 @@ class Engine:
                     t=t[:n].copy(), G=G[:n * K].reshape(n, K).copy(), aw_total=aw[:n].copy(),
                     aw_out=awg[:K, :n].copy(), aw_in=awg[K:, :n].copy())
 
-    def interest_point_paths(self, beta, eta, t_end, u, p, kappa, lam, r, delta, x0=1e-4, cap=65536) -> dict:
+    def interest_point_paths(self, beta, eta, t_end, u, p, kappa, lam, r, delta, x0=1e-4, cap=65536,
+                             ode_rtol: float | None = None, ode_atol: float | None = None,
+                             ode_maxiters: int | None = None) -> dict:
         """One interest-rate equilibrium with τ̄, HR(τ̄), V(τ̄) (saved on the HR grid) and
         AW_cum(τ̄) — what scripts/3_interest_rates.jl plots."""
         res = np.zeros(5)
         st = np.zeros(1, np.uint32)
         tau, hr, V, aw = np.empty(cap), np.empty(cap), np.empty(cap), np.empty(cap)
         nt, nv = ctypes.c_int64(), ctypes.c_int64()
-        opts = _lib.default_opts(early_exit_nan_run=0)
+        opts = _opts(ode_rtol, ode_atol, ode_maxiters, early_exit_nan_run=0)
         rc = self._L.sbr_interest_point_paths(self._ctx, beta, eta, t_end, x0, u, p, kappa, lam, r, delta,
                                               ctypes.byref(opts), _ptr(res), _ptr(st), _ptr(tau), _ptr(hr), _ptr(V),
                                               _ptr(aw), cap, ctypes.byref(nt), ctypes.byref(nv))
@@ -618,12 +657,15 @@ class Engine:
                     hr_tau=tau[:k].copy(), hr=hr[:k].copy(), V=V[:m].copy(), aw_cum=aw[:k].copy())
 
     def sweep_interest_dev(self, beta, eta, t_end, u, p, kappa, lam, r, delta, x0, out: dict,
-                           stream: int | None = None, max_iters: int = 100, knot_capacity: int = 65536):
+                           stream: int | None = None, max_iters: int = 100, knot_capacity: int = 65536,
+                           ode_rtol: float | None = None, ode_atol: float | None = None,
+                           ode_maxiters: int | None = None):
         """Device-pointer interest sweep on torch tensors (enqueue only)."""
         nb, nu = beta.numel(), u.numel()
         soa = _lib.ResultSoA(*_out_ptrs(out, (*RESULT_FIELDS, "status", "iters"), nb * nu,
                                         required=(*RESULT_FIELDS, "status")))
-        opts = _lib.default_opts(early_exit_nan_run=0, bisect_max_iters=max_iters, knot_capacity=knot_capacity)
+        opts = _opts(ode_rtol, ode_atol, ode_maxiters, early_exit_nan_run=0, bisect_max_iters=max_iters,
+                     knot_capacity=knot_capacity)
         (rk,) = _out_ptrs(out, ("rk_steps",), nb * nu)
         rc = self._L.sbr_sweep_interest_dev(self._ctx, stream, _dptr(beta, "beta", _F64), _dptr(eta, "eta", _F64, nb),
                                             _dptr(t_end, "t_end", _F64, nb), x0, _dptr(u, "u", _F64), nb, nu, p,
