@@ -95,6 +95,15 @@ typedef struct {
  * slope-monotone window (no early stop at the peak) and prunes with its bounds alone.  Same
  * results; with SBR_FLAG_DIAG_COUNT_AW_BLOCKS it shows what the window saves. */
 #define SBR_FLAG_DIAG_NO_AW_WINDOW 0x1000
+/* Heterogeneity entry points: solve the equilibria of any K with the group-looped kernel that
+ * serves the group counts without a specialised kernel (every K but 1, 2, 3, 4, 8), instead of
+ * the kernel specialised for that K.  Same results; for A/B timing and checks. */
+#define SBR_FLAG_HETERO_WIDE 0x2000
+
+/* Largest number of heterogeneity groups K (every heterogeneity entry point takes
+ * 1 <= K <= SBR_HETERO_MAX_K, SBR_EARG otherwise): the learning solve's Rosenbrock23 branch, a
+ * K×K LU, is pinned bit for bit against the CPU oracle up to 16 groups. */
+#define SBR_HETERO_MAX_K 16
 
 typedef struct {
     double* xi;          /* SolvedModel.ξ                       */
@@ -303,7 +312,8 @@ int sbr_equilibrium_on_knots_pdf(sbr_ctx* ctx, const double* t, const double* G,
  * and for each u:
  *     r  = solve_equilibrium_hetero(lr, EconomicParameters(u, p, κ, λ, η_bar, η))  heterogeneity_solver.jl:241
  *     get_AW_functions_hetero!(r).AW_max                                            heterogeneity_solver.jl:386
- * K ∈ {1, 2, 3, 4, 8}.  out->tau_in_unc/tau_out_unc are ignored; the per-group
+ * 1 <= K <= SBR_HETERO_MAX_K (K = 1, 2, 3, 4, 8 run kernels specialised for that K, every other K
+ * the group-looped kernels; SBR_FLAG_HETERO_WIDE).  out->tau_in_unc/tau_out_unc are ignored; the per-group
  * buffers go to tau_in/tau_out ([n_col*n_u][K], may be NULL).  The caller
  * resolves η = η_bar / Σ dist·βs per column (heterogeneity_model.jl:131-132).
  */

@@ -1049,6 +1049,14 @@ int sbr_sweep_baseline_dev(sbr_ctx* c, void* stream, const double* beta, const d
 // static LDS)); config 4 with Rosenbrock23 after the switch: n <= 7.9k knots
 constexpr int kHetLds = 10176;
 static int het_lds(const sbr_ctx* c) { return c->lds_cap * 3 < kHetLds ? c->lds_cap * 3 : kHetLds; }
+// the group counts every heterogeneity entry point takes (K = 1, 2, 3, 4, 8: specialised kernels,
+// the others: sbr_hetero_wide.hip / sbr_hetero_learn_wide.hip)
+static bool hetero_K_ok(int32_t K) { return K >= 1 && K <= SBR_HETERO_MAX_K; }
+static_assert(SBR_HETERO_MAX_K == 16, "kHeteroKMsg names the limit");
+static const char* const kHeteroKMsg =
+    "K must be between 1 and 16 (SBR_HETERO_MAX_K): the learning solve's Rosenbrock23 branch, a K x K LU, is "
+    "pinned against the oracle up to 16 groups";
+static bool hetero_wide(const sbr_opts& o) { return (o.flags & SBR_FLAG_HETERO_WIDE) != 0; }
 
 
 int sbr_sweep_baseline_batch_dev(sbr_ctx* c, void* stream, int64_t n_batch, const double* beta, const double* eta,
@@ -1632,19 +1640,21 @@ int ensure_knots(sbr_ctx* c, size_t n, size_t n_u)
 }
 
 // sbr_hetero_equilibrium_on_knots' device block (and pinned mirror) for ck knots, cu u values and
-// K <= 8 groups: [counters | βs, dist, η | t, G packed by the call's n | HR, I (K·ck each) |
-// t_end, u | results, buffers, AW_total path]
+// K <= SBR_HETERO_MAX_K groups: [counters | βs, dist, η | t, G packed by the call's n | HR, I (K·ck
+// each) | t_end, u | results, buffers, AW_total path]
 struct HeteroKnotLayout {
     size_t sc, tg, hr, hri, u, res, bytes;
     HeteroKnotLayout(size_t ck, size_t cu)
     {
+        constexpr size_t KM = SBR_HETERO_MAX_K;
         sc = 64;
-        tg = 256;
-        hr = tg + 8 * ck * 9;
-        hri = hr + 8 * ck * 8;
-        u = hri + 8 * ck * 8;
+        tg = 512; // sc + (2·KM + 1) doubles, rounded up
+        static_assert(64 + 8 * (2 * KM + 1) <= 512, "βs, dist, η in front of the knots");
+        hr = tg + 8 * ck * (KM + 1);
+        hri = hr + 8 * ck * KM;
+        u = hri + 8 * ck * KM;
         res = u + 8 * (cu + 8);
-        bytes = res + 8 * (5 * cu + 16 * cu + 17 * ck) + 256; // path mode: AW_total + 2K group rows
+        bytes = res + 8 * (5 * cu + 2 * KM * cu + (2 * KM + 1) * ck) + 256; // path mode: AW_total + 2K group rows
     }
 };
 
@@ -1693,7 +1703,7 @@ int sbr_hetero_equilibrium_on_knots(sbr_ctx* c, int32_t K, const double* t, cons
     if (guess_set(opts)) return fail(c, SBR_EARG, "xi_guess: only sbr_equilibrium_on_knots takes a first iterate");
     SBR_ON_RANK0(c, sbr_hetero_equilibrium_on_knots(c, K, t, G, n, betas, dist, eta, t_end, u, n_u, p, kappa, lambda, opts, out, tau_in, tau_out, hr, aw_total, aw_groups, cap, n_tau));
     if (!c || !t || !G || !betas || !dist || !u || !out) return SBR_EARG;
-    if (K != 1 && K != 2 && K != 3 && K != 4 && K != 8) return fail(c, SBR_EARG, "K must be 1, 2, 3, 4 or 8");
+    if (!hetero_K_ok(K)) return fail(c, SBR_EARG, kHeteroKMsg);
     if (n < 1 || n > (1 << 24) || n_u < 1 || n_u > (1 << 24)) return fail(c, SBR_EARG, "knot / u count");
     double dsum = 0.0;
     for (int k = 0; k < K; k++) {
@@ -1780,8 +1790,8 @@ int sbr_hetero_equilibrium_on_knots(sbr_ctx* c, int32_t K, const double* t, cons
                              (o.flags & SBR_FLAG_EXHAUSTIVE) ? 1 : 0, (o.flags >> 8) & 7, aw_total ? dpath : nullptr};
         const sbr::ResultSoA r{dres, nullptr, nullptr, dres + nu, dres + 2 * nu, (uint32_t*)(dres + 3 * nu),
                                (int32_t*)(dres + 3 * nu) + nu};
-        HIP_TRY(c, sbr::launch_hetero(K, dsc, dsc + K, dsc + 2 * K, du, du + 1, la, ea, HB, r, dtin, dtout, s, 1),
-                SBR_EDEVICE);
+        HIP_TRY(c, sbr::launch_hetero(K, dsc, dsc + K, dsc + 2 * K, du, du + 1, la, ea, HB, r, dtin, dtout, s, 1,
+                                      hetero_wide(o)), SBR_EDEVICE);
         if (aw_groups)
             HIP_TRY(c, sbr::launch_hetero_aw_groups(K, dtg, dtg + n, dcnt, (int)n, dres, dtin, dtout,
                                                     (const uint32_t*)(dres + 3 * nu), dpath + n, (size_t)n, s),
@@ -2118,7 +2128,7 @@ int sbr_learn_hetero(sbr_ctx* c, int32_t K, const double* betas, const double* d
     if (guess_set(opts)) return fail(c, SBR_EARG, "xi_guess: only sbr_equilibrium_on_knots takes a first iterate");
     SBR_ON_RANK0(c, sbr_learn_hetero(c, K, betas, dist, t_end, x0, n_col, opts, t_out, G_out, cap, n_knots, status));
     if (!c || !betas || !dist || !t_end || n_col <= 0 || n_col > (1 << 30) || cap <= 0) return SBR_EARG;
-    if (K != 1 && K != 2 && K != 3 && K != 4 && K != 8) return fail(c, SBR_EARG, "K must be 1, 2, 3, 4 or 8");
+    if (!hetero_K_ok(K)) return fail(c, SBR_EARG, kHeteroKMsg);
     // LearningParametersHetero checks (heterogeneity_model.jl:33-41)
     double dsum = 0.0;
     for (int k = 0; k < K; k++) {
@@ -2175,7 +2185,7 @@ int sbr_sweep_hetero_dev(sbr_ctx* c, void* stream, int32_t K, const double* beta
     if (guess_set(opts)) return fail(c, SBR_EARG, "xi_guess: only sbr_equilibrium_on_knots takes a first iterate");
     SBR_SINGLE_DEVICE(c);
     if (!c || !out || !out->xi || !out->aw_max || !out->tol || !out->status) return SBR_EARG;
-    if (K != 1 && K != 2 && K != 3 && K != 4 && K != 8) return fail(c, SBR_EARG, "K must be 1, 2, 3, 4 or 8");
+    if (!hetero_K_ok(K)) return fail(c, SBR_EARG, kHeteroKMsg);
     if (n_col <= 0 || n_u <= 0 || n_col > (1 << 30) || n_u > (1 << 30)) return fail(c, SBR_EARG, "grid size");
     if (!scalars_valid(x0, p, kappa, lambda)) return fail(c, SBR_EARG, "ArgumentError: x0/p/kappa/lambda");
     if (hipSetDevice(c->device) != hipSuccess) return fail(c, SBR_EDEVICE, "hipSetDevice");
@@ -2191,7 +2201,8 @@ int sbr_sweep_hetero_dev(sbr_ctx* c, void* stream, int32_t K, const double* beta
         HIP_TRY(c, sbr::launch_hetero(K, betas, dist, eta, t_end, u, la, ea, c->H, r, tau_in, tau_out, s, 0), SBR_EDEVICE);
         tend(c, s, 0, t0);
         t0 = tstart(c, s);
-        HIP_TRY(c, sbr::launch_hetero(K, betas, dist, eta, t_end, u, la, ea, c->H, r, tau_in, tau_out, s, 1), SBR_EDEVICE);
+        HIP_TRY(c, sbr::launch_hetero(K, betas, dist, eta, t_end, u, la, ea, c->H, r, tau_in, tau_out, s, 1, hetero_wide(o)),
+                SBR_EDEVICE);
         tend(c, s, 1, t0);
         return SBR_OK;
     });
@@ -2206,7 +2217,7 @@ int sbr_sweep_hetero_batch_dev(sbr_ctx* c, void* stream, int64_t n_batch, int32_
     SBR_SINGLE_DEVICE(c);
     if (!c || !out || !out->xi || !out->aw_max || !out->tol || !out->status || !betas || !dist || !eta || !t_end || !u)
         return SBR_EARG;
-    if (K != 1 && K != 2 && K != 3 && K != 4 && K != 8) return fail(c, SBR_EARG, "K must be 1, 2, 3, 4 or 8");
+    if (!hetero_K_ok(K)) return fail(c, SBR_EARG, kHeteroKMsg);
     if (n_batch <= 0 || n_col <= 0 || n_u <= 0 || n_col > (1 << 30) || n_u > (1 << 30))
         return fail(c, SBR_EARG, "grid size");
     if (!scalars_valid(x0, p, kappa, lambda)) return fail(c, SBR_EARG, "ArgumentError: x0/p/kappa/lambda");
@@ -2243,7 +2254,7 @@ int sbr_sweep_hetero_batch_dev(sbr_ctx* c, void* stream, int64_t n_batch, int32_
             HIP_TRY(c, hipEventRecord(c->ev_learned[slot], ls), SBR_EDEVICE);
             HIP_TRY(c, hipStreamWaitEvent(s, c->ev_learned[slot], 0), SBR_EDEVICE);
             t0 = tstart(c, s);
-            HIP_TRY(c, sbr::launch_hetero(K, bk, dist, ek, tk, u, la, ea, H, r, ti, to, s, 1), SBR_EDEVICE);
+            HIP_TRY(c, sbr::launch_hetero(K, bk, dist, ek, tk, u, la, ea, H, r, ti, to, s, 1, hetero_wide(o)), SBR_EDEVICE);
             tend(c, s, 1, t0);
             HIP_TRY(c, hipEventRecord(c->ev_eq[slot], s), SBR_EDEVICE);
         }
@@ -2259,7 +2270,7 @@ int sbr_hetero_point_paths(sbr_ctx* c, int32_t K, const double* betas, const dou
     if (guess_set(opts)) return fail(c, SBR_EARG, "xi_guess: only sbr_equilibrium_on_knots takes a first iterate");
     SBR_ON_RANK0(c, sbr_hetero_point_paths(c, K, betas, dist, eta, t_end, x0, u, p, kappa, lambda, opts, res, status, tau_in, tau_out, t, G, aw_total, aw_groups, cap, n_knots));
     if (!c || !res || !status || !betas || !dist) return SBR_EARG;
-    if (K != 1 && K != 2 && K != 3 && K != 4 && K != 8) return fail(c, SBR_EARG, "K must be 1, 2, 3, 4 or 8");
+    if (!hetero_K_ok(K)) return fail(c, SBR_EARG, kHeteroKMsg);
     double dsum = 0.0;
     for (int k = 0; k < K; k++) {
         if (!(dist[k] >= 0.0)) return fail(c, SBR_EARG, "ArgumentError: distribution weights must be non-negative");
@@ -2324,7 +2335,8 @@ int sbr_sweep_hetero(sbr_ctx* c, int32_t K, const double* betas, const double* d
                      double* tau_out)
 {
     if (guess_set(opts)) return fail(c, SBR_EARG, "xi_guess: only sbr_equilibrium_on_knots takes a first iterate");
-    if (!c || !out || !betas || !dist || !eta || !t_end || !u || K <= 0) return SBR_EARG;
+    if (!c || !out || !betas || !dist || !eta || !t_end || !u) return SBR_EARG;
+    if (!hetero_K_ok(K)) return fail(c, SBR_EARG, kHeteroKMsg); // before dist[0 .. K) is read
     if (n_col <= 0 || n_u <= 0) return fail(c, SBR_EARG, "grid size");
     // LearningParametersHetero checks (heterogeneity_model.jl:33-41)
     double dsum = 0.0;
@@ -2340,7 +2352,6 @@ int sbr_sweep_hetero(sbr_ctx* c, int32_t K, const double* betas, const double* d
     for (int64_t j = 0; j < n_u; j++)
         if (!(u[j] >= 0.0)) return fail(c, SBR_EARG, "ArgumentError: u must be non-negative");
     if (c->multi) {
-        if (K != 1 && K != 2 && K != 3 && K != 4 && K != 8) return fail(c, SBR_EARG, "K must be 1, 2, 3, 4 or 8");
         return multi_sweep_hetero(c, K, betas, dist, eta, t_end, x0, u, n_col, n_u, p, kappa, lambda, resolve(opts),
                                   out, tau_in, tau_out);
     }

@@ -225,7 +225,21 @@ hipError_t launch_hetero_aw_groups(int K, const double* T, const double* G, cons
                                    double* out, size_t ld, hipStream_t s);
 hipError_t launch_hetero(int K, const double* betas, const double* dist, const double* eta, const double* t_end,
                          const double* u, const LearnArgs& la, const HeteroEqArgs& ea, const HeteroBufs& L,
-                         const ResultSoA& out, double* tin, double* tout, hipStream_t s, int phase);
+                         const ResultSoA& out, double* tin, double* tout, hipStream_t s, int phase,
+                         bool wide = false);
+// What launch_hetero / launch_hetero_aw_groups route to for the group counts that have no
+// specialised kernels (every K in [1, SBR_HETERO_MAX_K] but 1, 2, 3, 4, 8), and the equilibria of any K
+// with `wide` (SBR_FLAG_HETERO_WIDE): the group-looped equilibrium kernel with K a runtime argument
+// (sbr_hetero_wide.hip), the learning (phase 0) / hazard (phase 2) kernels of sbr_hetero_learn_wide.hip
+hipError_t launch_hetero_wide(int K, const double* dist, const double* eta, const double* t_end, const double* u,
+                              const LearnArgs& la, const HeteroEqArgs& ea, const HeteroBufs& L, const ResultSoA& out,
+                              double* tin, double* tout, hipStream_t s);
+hipError_t launch_hetero_learn_wide(int K, const double* betas, const double* dist, const double* eta,
+                                    const double* t_end, const LearnArgs& la, const HeteroBufs& L, hipStream_t s,
+                                    int phase);
+hipError_t launch_hetero_aw_groups_wide(int K, const double* T, const double* G, const int32_t* n_dev, int n_max,
+                                        const double* xi, const double* tin, const double* tout,
+                                        const uint32_t* status, double* out, size_t ld, hipStream_t s);
 
 hipError_t launch_learn_logistic(const double* beta, const double* eta, const double* t_end, const LearnArgs& a,
                                  const LearnBufs& L, hipStream_t s);

@@ -25,6 +25,10 @@ heterogeneity_solver.jl by this file.  Then :59, :67 and :76 run unchanged:
 
 A β×u (or βs-column × u) grid is one call: `SBREngine.solve_equilibrium_hetero_grid`.
 
+`length(βs)` goes to the engine as it is: any number of groups from 1 to 16 (SBR_HETERO_MAX_K)
+runs on the GPU; beyond 16 the engine returns an argument error (the CPU oracle that pins the
+Rosenbrock23 branch has no Jacobian past 16 groups).
+
 NOT EXECUTED IN THIS REPOSITORY (no Julia in the image): the same entry points run through
 the Python binding (sbr.learn_hetero / hetero_point_paths, tests/test_hetero.py), and
 tests/test_julia_shim.py checks this file's call surface against the reference's

@@ -241,6 +241,9 @@ end
     solve_equilibrium_hetero_grid(ctx, βs_cols, dist, u_vals; η, tspan_end, x0, p, κ, λ)
 
 `βs_cols` is K × n_col (column c = the group rates of one parameter column); η per column.
+Any number of groups 1 ≤ K ≤ 16 (SBR_HETERO_MAX_K of include/sbr.h; `length(βs)` is passed
+through, a larger K is an ArgumentError from the engine) — here and in `learn_hetero`,
+`hetero_equilibrium_on_knots` and `solve_hetero_point_paths`.
 """
 function solve_equilibrium_hetero_grid(ctx::Context, βs_cols::AbstractMatrix, dist, u_vals; η, tspan_end,
                                        x0 = 1e-4, p = 0.9, κ = 0.3, λ = 0.1)

@@ -31,6 +31,8 @@ SBR_FLAG_DIAG_STOP_AFTER_BISECT = 0x200
 SBR_FLAG_DIAG_COUNT_AW_BLOCKS = 0x400
 SBR_FLAG_DIAG_SOCIAL_PROF = 0x800
 SBR_FLAG_DIAG_NO_AW_WINDOW = 0x1000
+SBR_FLAG_HETERO_WIDE = 0x2000
+SBR_HETERO_MAX_K = 16
 
 
 class SBRNativeError(RuntimeError):

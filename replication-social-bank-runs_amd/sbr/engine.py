@@ -389,13 +389,14 @@ class Engine:
         return out
 
     def hetero_equilibrium_on_knots(self, t, G, betas, dist, eta, t_end, u, p, kappa, lam,
-                                    paths: bool = True, exhaustive: bool = False) -> dict:
+                                    paths: bool = True, exhaustive: bool = False, wide: bool = False) -> dict:
         """solve_equilibrium_hetero(lr_hetero, econ) + get_AW_functions_hetero! on the knots a
         LearningResultsHetero holds (t [n], G [n, K] = the learning_cdfs' values) for each u — no
         learning ODE (sbr_hetero_equilibrium_on_knots; knots, CDFs and the K hazards stay on the
         GPU while the inputs repeat).  Per-u arrays, buffers [n_u, K]; with ``paths`` (one u) HR_k
         on the τ̄ grid [K, n_tau], AW_total on the knots and get_AW_hetero's per-group curves
-        aw_out / aw_in [K, n] (heterogeneity_solver.jl:335-362; NaN without a run)."""
+        aw_out / aw_in [K, n] (heterogeneity_solver.jl:335-362; NaN without a run).  1 <= K <= 16;
+        ``wide`` (SBR_FLAG_HETERO_WIDE): the group-looped equilibrium kernel at any K, same results."""
         t = np.ascontiguousarray(t, np.float64)
         G = np.ascontiguousarray(G, np.float64)
         betas = np.ascontiguousarray(betas, np.float64)
@@ -417,7 +418,8 @@ class Engine:
         aw = np.empty(cap) if paths else None
         awg = np.empty((2 * K, cap)) if paths else None
         nt = ctypes.c_int64()
-        opts = _lib.default_opts(early_exit_nan_run=0, flags=_lib.SBR_FLAG_EXHAUSTIVE if exhaustive else 0)
+        opts = _lib.default_opts(early_exit_nan_run=0, flags=(_lib.SBR_FLAG_EXHAUSTIVE if exhaustive else 0)
+                                 | (_lib.SBR_FLAG_HETERO_WIDE if wide else 0))
         rc = self._L.sbr_hetero_equilibrium_on_knots(self._ctx, K, _ptr(t), _ptr(G), n, _ptr(betas), _ptr(dist), eta,
                                                      t_end, _ptr(u), nu, p, kappa, lam, ctypes.byref(opts),
                                                      ctypes.byref(soa), _ptr(tin), _ptr(tout), _ptr(hr), _ptr(aw),
@@ -431,10 +433,11 @@ class Engine:
 
     def sweep_hetero(self, betas, dist, eta, t_end, u, p, kappa, lam, x0=1e-4, knot_capacity: int = 16384,
                      with_groups: bool = True, exhaustive: bool = False, ode_rtol: float | None = None,
-                     ode_atol: float | None = None, ode_maxiters: int | None = None) -> dict:
-        """Heterogeneity sweep: ``betas`` [n_col, K] group rates per column,
+                     ode_atol: float | None = None, ode_maxiters: int | None = None, wide: bool = False) -> dict:
+        """Heterogeneity sweep: ``betas`` [n_col, K] group rates per column (1 <= K <= 16),
         ``eta``/``t_end`` per column, every u.  Returns [n_col, n_u] arrays and,
-        with ``with_groups``, per-group buffers [n_col, n_u, K]."""
+        with ``with_groups``, per-group buffers [n_col, n_u, K].  ``wide`` (SBR_FLAG_HETERO_WIDE,
+        tests and timing): the group-looped equilibrium kernel at any K, same results."""
         betas = np.ascontiguousarray(np.atleast_2d(betas), np.float64)
         n_col, K = betas.shape
         dist = np.ascontiguousarray(dist, np.float64)
@@ -450,7 +453,8 @@ class Engine:
         soa = _lib.ResultSoA(_ptr(out["xi"]), None, None, _ptr(out["aw_max"]), _ptr(out["tol"]),
                              _ptr(out["status"]), _ptr(out["iters"]))
         opts = _opts(ode_rtol, ode_atol, ode_maxiters, knot_capacity=knot_capacity,
-                     flags=_lib.SBR_FLAG_EXHAUSTIVE if exhaustive else 0)
+                     flags=(_lib.SBR_FLAG_EXHAUSTIVE if exhaustive else 0)
+                     | (_lib.SBR_FLAG_HETERO_WIDE if wide else 0))
         rc = self._L.sbr_sweep_hetero(self._ctx, K, _ptr(betas), _ptr(dist), _ptr(eta), _ptr(t_end), x0, _ptr(u),
                                       n_col, nu, p, kappa, lam, ctypes.byref(opts), ctypes.byref(soa), _ptr(tin),
                                       _ptr(tout))
@@ -464,8 +468,9 @@ class Engine:
     def sweep_hetero_dev(self, K, betas, dist, eta, t_end, u, p, kappa, lam, x0, out: dict,
                          stream: int | None = None, knot_capacity: int = 16384, flags: int = 0,
                          ode_rtol: float | None = None, ode_atol: float | None = None,
-                         ode_maxiters: int | None = None):
-        """Device-pointer hetero sweep on torch tensors (no host sync)."""
+                         ode_maxiters: int | None = None, wide: bool = False):
+        """Device-pointer hetero sweep on torch tensors (no host sync).  ``wide``: SBR_FLAG_HETERO_WIDE."""
+        flags |= _lib.SBR_FLAG_HETERO_WIDE if wide else 0
         n_col, nu = eta.numel(), u.numel()
         xi, aw, tl, st, it = _out_ptrs(out, ("xi", "aw_max", "tol", "status", "iters"), n_col * nu,
                                        required=("xi", "aw_max", "tol", "status"))
@@ -480,10 +485,11 @@ class Engine:
     def sweep_hetero_batch_dev(self, K, betas, dist, eta, t_end, u, p, kappa, lam, x0, out: dict,
                                stream: int | None = None, knot_capacity: int = 16384, flags: int = 0,
                                ode_rtol: float | None = None, ode_atol: float | None = None,
-                               ode_maxiters: int | None = None):
+                               ode_maxiters: int | None = None, wide: bool = False):
         """Pipelined hetero sweep of several grids on torch tensors (see
         sbr_sweep_hetero_batch_dev): ``betas`` [n_batch, n_col, K], ``eta``/``t_end``
-        [n_batch, n_col], every ``out`` tensor [n_batch, n_col * n_u]."""
+        [n_batch, n_col], every ``out`` tensor [n_batch, n_col * n_u].  ``wide``: SBR_FLAG_HETERO_WIDE."""
+        flags |= _lib.SBR_FLAG_HETERO_WIDE if wide else 0
         nbat, n_col = eta.shape
         nu = u.numel()
         if tuple(betas.shape) != (nbat, n_col, K) or tuple(t_end.shape) != (nbat, n_col):
@@ -615,7 +621,7 @@ class Engine:
 
     def hetero_point_paths(self, betas, dist, eta, t_end, u, p, kappa, lam, x0=1e-4, cap=65536,
                            ode_rtol: float | None = None, ode_atol: float | None = None,
-                           ode_maxiters: int | None = None) -> dict:
+                           ode_maxiters: int | None = None, wide: bool = False) -> dict:
         """One heterogeneity equilibrium with learning knots t, group CDFs G [n, K], the
         per-group buffers, AW_total(t) and the per-group AW_OUT_k / AW_IN_k curves on the knots
         (aw_out / aw_in [K, n]) — what scripts/2_heterogeneity.jl plots."""
@@ -628,7 +634,8 @@ class Engine:
         t, G, aw = np.empty(cap), np.empty(cap * K), np.empty(cap)
         awg = np.empty((2 * K, cap))
         nk = ctypes.c_int64()
-        opts = _opts(ode_rtol, ode_atol, ode_maxiters, early_exit_nan_run=0, knot_capacity=16384)
+        opts = _opts(ode_rtol, ode_atol, ode_maxiters, early_exit_nan_run=0, knot_capacity=16384,
+                     flags=_lib.SBR_FLAG_HETERO_WIDE if wide else 0)
         rc = self._L.sbr_hetero_point_paths(self._ctx, K, _ptr(betas), _ptr(dist), eta, t_end, x0, u, p, kappa, lam,
                                             ctypes.byref(opts), _ptr(res), _ptr(st), _ptr(tin), _ptr(tout), _ptr(t),
                                             _ptr(G), _ptr(aw), _ptr(awg), cap, ctypes.byref(nk))
