@@ -247,6 +247,51 @@ int sbr_solve_points_dev(sbr_ctx* ctx, void* stream, const double* beta, const d
 int sbr_set_points_workspace(sbr_ctx* ctx, int64_t bytes);
 
 /*
+ * Comparative statics in every economic parameter at once — β × p × λ × κ × u, the product of five
+ * axes, learning each β once:
+ *     lr = solve_learning(LearningParameters(beta[i], (0, t_end[i]), x0))            once per column
+ *     solve_equilibrium_baseline(lr, EconomicParameters(u[j], p[a], kappa[c], lambda[b], η_bar, eta[i]))
+ * (scripts/1_baseline.jl:44, 169).  The learning solve depends on (β, t_end, x0) only, the hazard
+ * path on (column, η, p, λ) — one per column and class (a, b) — and κ and u enter only the
+ * per-point solve.  Every out field has n_beta·n_p·n_lambda·n_kappa·n_u entries (iters may be
+ * NULL), element (i, a, b, c, j) at ((((i·n_p + a)·n_lambda + b)·n_kappa + c)·n_u + j): the κ × u
+ * plane of one hazard path is contiguous and u-fastest.  The line [i, a, b, c, :] is exactly row i
+ * of sbr_sweep_baseline(beta, eta, t_end, x0, u, …, p[a], kappa[c], lambda[b], opts): all seven
+ * fields and the status bits, the learning bits included, at any tolerances and caps.
+ * η is per column, as in sbr_sweep_baseline (the learning truncation and the column's learning
+ * bits are tied to it); a per-row η is not offered.
+ * SBR_EARG as sbr_sweep_baseline for beta, eta, t_end, u and x0, and for an axis element that
+ * breaks 0 <= p <= 1, 0 < κ < 1 or λ > 0 (a NaN breaks its rule), a non-positive axis length, a
+ * null array, SBR_FLAG_XI_GUESS.  Host pointers; synchronous; a failed call writes none of the
+ * caller's arrays.  opts->early_exit_nan_run is applied per u-line:
+ * sbr_apply_early_exit(n_beta·n_p·n_lambda·n_kappa, n_u, …).  SBR_FLAG_EXHAUSTIVE is honoured,
+ * SBR_FLAG_READY_SWEEP ignored.  On an n-device context the columns are dealt cyclically, over
+ * either transport.
+ * Workspace: the learning rows (4 × knot_capacity × 8 + 24 bytes per column) and, per class in
+ * flight, one HR row and three counters per column (knot_capacity × 8 + 12 bytes).  With budget B
+ * (sbr_set_econ_workspace), max(1, (B − learning) / (n_beta × (knot_capacity × 8 + 12))) classes run
+ * per chunk, the chunks in stream order through the same rows; the results do not depend on the
+ * chunking.
+ */
+int sbr_sweep_econ(sbr_ctx* ctx, const double* beta, const double* eta, const double* t_end, double x0,
+                   const double* u, int64_t n_beta, int64_t n_u, const double* p, int64_t n_p,
+                   const double* lambda, int64_t n_lambda, const double* kappa, int64_t n_kappa,
+                   const sbr_opts* opts, sbr_result_soa* out);
+/* Same on device pointers (the seven arrays and every out field in HBM), enqueued on `stream`; no
+ * host synchronisation and no early-exit post-pass.  The axes cannot be read on the host: a point
+ * whose own u, p, κ or λ breaks its rule ends with status == SBR_ARG_INVALID, ξ = τ̄_IN = τ̄_OUT =
+ * AW_max = NaN, tol = Inf, iters = 0 (as in sbr_solve_points), and no other point is touched.
+ * Needs a single-device context. */
+int sbr_sweep_econ_dev(sbr_ctx* ctx, void* stream, const double* beta, const double* eta, const double* t_end,
+                       double x0, const double* u, int64_t n_beta, int64_t n_u, const double* p, int64_t n_p,
+                       const double* lambda, int64_t n_lambda, const double* kappa, int64_t n_kappa,
+                       const sbr_opts* opts, sbr_result_soa* out);
+/* Budget in bytes for the workspace of sbr_sweep_econ[_dev] (0 = 40 % of the free plus already held
+ * HBM at call time): it caps the classes per chunk, at least one.  An allocation that fails anyway
+ * halves the chunk and retries.  An n-device context sets every rank's budget. */
+int sbr_set_econ_workspace(sbr_ctx* ctx, int64_t bytes);
+
+/*
  * Learning only — solve_learning (learning.jl:109-124) for n_beta β at once.
  * Writes, per β, the knot grid t and CDF values G of the adaptive ODE
  * solution (row i at [i*cap .. i*cap + n_knots[i]) ); g = βG(1−G) is implied

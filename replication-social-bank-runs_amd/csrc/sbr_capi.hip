@@ -135,6 +135,12 @@ struct sbr_ctx {
     int64_t n_grid = 0;
     int64_t bt_budget = 0; // baseline batch learning workspaces, bytes (0: 40 % of free + held HBM)
     int64_t pt_budget = 0; // learning workspace of a list of models (sbr_solve_points), bytes (0: the same default)
+    // sbr_sweep_econ: HR rows, τ̄ counters and status words of the hazard classes in flight
+    // (ec_rows rows of stride ec_ld: classes per chunk × columns), and its budget in bytes
+    double* ec_hr = nullptr;
+    int32_t* ec_cnt = nullptr; // n_tau [ec_rows], n_le [ec_rows], status [ec_rows]
+    size_t ec_rows = 0, ec_ld = 0;
+    int64_t ec_budget = 0; // 0: 40 % of the free plus the already held HBM
     size_t ev_used = 0;
     struct TRec {
         int kind; // 0 learning (+ hazard), 1 equilibrium
@@ -822,6 +828,100 @@ int run_points(sbr_ctx* c, hipStream_t s, const double* beta, const double* eta,
     return SBR_OK;
 }
 
+void free_econ(sbr_ctx* c)
+{
+    if (c->ec_hr) (void)hipFree(c->ec_hr);
+    if (c->ec_cnt) (void)hipFree(c->ec_cnt);
+    c->ec_hr = nullptr;
+    c->ec_cnt = nullptr;
+    c->ec_rows = c->ec_ld = 0;
+}
+
+int ensure_econ(sbr_ctx* c, size_t rows, size_t ld)
+{
+    if (rows <= c->ec_rows && ld == c->ec_ld) return SBR_OK;
+    free_econ(c);
+    HIP_TRY(c, hipMalloc(&c->ec_hr, rows * ld * sizeof(double)), SBR_ENOMEM);
+    HIP_TRY(c, hipMalloc(&c->ec_cnt, rows * 3 * sizeof(int32_t)), SBR_ENOMEM);
+    c->ec_rows = rows;
+    c->ec_ld = ld;
+    return SBR_OK;
+}
+
+// workspace bytes a (column, class) pair counts for against the budget (sbr.h: sbr_sweep_econ)
+size_t econ_class_bytes(size_t cap) { return cap * sizeof(double) + 3 * sizeof(int32_t); }
+
+// β × p × λ × κ × u (sbr_sweep_econ), all in stream order on s: the learning launch of a single
+// sweep once (one lane per column, truncated after η at default opts, no hazard), then per chunk
+// of hazard classes (p[a], λ[b]) the hazard launch — one workgroup per (column, class) — and the
+// equilibrium launches over the κ × u planes.  A chunk's hazards start after the previous
+// chunk's equilibria (they share the class rows); no host synchronisation.  Timing records:
+// kind 0 = the learning launch, kind 1 = the hazard and equilibrium launches.
+int run_econ(sbr_ctx* c, hipStream_t s, const double* beta, const double* eta, const double* t_end, double x0,
+             const double* u, int64_t n_beta, int64_t n_u, const double* p, int64_t n_p, const double* lambda,
+             int64_t n_lambda, const double* kappa, int64_t n_kappa, const sbr_opts& o, const sbr::ResultSoA& out)
+{
+    const size_t cap = (size_t)o.knot_capacity;
+    const int64_t n_class = n_p * n_lambda;
+    size_t freeb = 0, total = 0;
+    (void)hipMemGetInfo(&freeb, &total);
+    const size_t held = c->ws_beta[0] * batch_col_bytes(c->ws_cap[0]) + c->ec_rows * c->ec_ld * sizeof(double);
+    const double budget = c->ec_budget > 0 ? (double)c->ec_budget : 0.4 * (double)(freeb + held);
+    const double left = budget - (double)n_beta * (double)point_bytes(cap);
+    int64_t per = left > 0.0 ? (int64_t)std::min(left / ((double)n_beta * (double)econ_class_bytes(cap)), 65535.0) : 1;
+    per = std::max<int64_t>(1, std::min<int64_t>(per, n_class));
+    int rc = ensure_learn(c, (size_t)n_beta, cap);
+    if (rc) return rc;
+    c->last_slot = 0;
+    c->last_off = 0;
+    c->rs_used = false;
+    const sbr::LearnBufs& L = c->LW[0];
+    // a workspace that already holds enough rows of this stride is used as it is
+    for (;;) {
+        rc = ensure_econ(c, (size_t)(per * n_beta), (size_t)L.cap);
+        if (rc == SBR_OK) break;
+        free_econ(c);
+        if (per == 1) return rc;
+        (void)hipGetLastError(); // the failed hipMalloc's error must not surface at the next launch check
+        per = (per + 1) / 2;
+    }
+    // p and λ are per class: the hazard runs in hazard_econ_kernel, not in the learning launch
+    sbr::LearnArgs la{x0, o.ode_reltol, o.ode_abstol, 0.0, 0.0, o.ode_maxiters, (int32_t)n_beta, stop_after_eta(o), 0};
+    hipEvent_t t0 = tstart(c, s);
+    HIP_TRY(c, sbr::launch_learn_kernel(beta, eta, t_end, la, L, s, 1), SBR_EDEVICE);
+    tend(c, s, 0, t0);
+    sbr::EqArgs ea{0.0, (int32_t)(n_kappa * n_u), o.bisect_max_iters, c->lds_cap_b, nullptr,
+                   (o.flags & SBR_FLAG_EXHAUSTIVE) ? 1 : 0, (o.flags >> 8) & 0x17};
+    t0 = tstart(c, s);
+    int launches = 0;
+    for (int64_t g0 = 0; g0 < n_class; g0 += per) {
+        const int64_t ng = std::min<int64_t>(per, n_class - g0);
+        const size_t rows = (size_t)(per * n_beta);
+        const sbr::EconArgs e{p, lambda, kappa, (int32_t)n_p, (int32_t)n_lambda, (int32_t)n_kappa, (int32_t)n_u,
+                              (int32_t)n_beta, (int32_t)g0, (int32_t)ng, c->ec_hr, c->ec_cnt, c->ec_cnt + rows,
+                              (uint32_t*)(c->ec_cnt + 2 * rows)};
+        HIP_TRY(c, sbr::launch_hazard_econ(beta, eta, la, L, e, s), SBR_EDEVICE);
+        HIP_TRY(c, sbr::launch_equilibrium_econ(L, eta, t_end, u, ea, e, out, s), SBR_EDEVICE);
+        launches += 3;
+    }
+    tend(c, s, 1, t0, launches);
+    return SBR_OK;
+}
+
+// the checks sbr_sweep_econ and sbr_sweep_econ_dev share, before any array is looked at
+int econ_checks(sbr_ctx* c, const sbr_opts* opts, double x0, int64_t n_beta, int64_t n_u, int64_t n_p,
+                int64_t n_lambda, int64_t n_kappa)
+{
+    if (guess_set(opts)) return fail(c, SBR_EARG, "xi_guess: only sbr_equilibrium_on_knots takes a first iterate");
+    if (!c) return SBR_EARG;
+    const int64_t lim = 1 << 30;
+    if (n_beta <= 0 || n_u <= 0 || n_p <= 0 || n_lambda <= 0 || n_kappa <= 0 || n_beta > lim || n_u > lim ||
+        n_p > lim || n_lambda > lim || n_kappa > lim || n_p * n_lambda > lim || n_kappa * n_u > lim)
+        return fail(c, SBR_EARG, "grid size");
+    if (!(x0 >= 0.0)) return fail(c, SBR_EARG, "ArgumentError: x0");
+    return SBR_OK;
+}
+
 int run_interest(sbr_ctx* c, hipStream_t s, const double* beta, const double* eta, const double* t_end, double x0,
                  const double* u, int64_t n_beta, int64_t n_u, double p, double kappa, double lambda, double r,
                  double delta, const sbr_opts& o, const sbr::ResultSoA& out, int64_t* steps, double* aw_path = nullptr,
@@ -865,6 +965,9 @@ int multi_sweep_baseline(sbr_ctx* c, const double* beta, const double* eta, cons
 int multi_solve_points(sbr_ctx* c, const double* beta, const double* eta, const double* t_end, double x0,
                        const double* u, const double* p, const double* kappa, const double* lambda, int64_t n,
                        const sbr_opts& o, sbr_result_soa* out);
+int multi_sweep_econ(sbr_ctx* c, const double* beta, const double* eta, const double* t_end, double x0,
+                     const double* u, int64_t n_beta, int64_t n_u, const double* p, int64_t n_p, const double* lambda,
+                     int64_t n_lambda, const double* kappa, int64_t n_kappa, const sbr_opts& o, sbr_result_soa* out);
 
 }  // namespace
 
@@ -985,6 +1088,7 @@ int sbr_free(sbr_ctx* c)
     free_hetero(c);
     free_social(c);
     free_pool(c);
+    free_econ(c);
     if (c->so_prof) (void)hipFree(c->so_prof);
     if (c->so_count_host) (void)hipHostFree(c->so_count_host);
     if (c->so_args_dev) (void)hipFree(c->so_args_dev);
@@ -1379,6 +1483,106 @@ int sbr_set_points_workspace(sbr_ctx* c, int64_t bytes)
         return SBR_OK;
     }
     c->pt_budget = bytes;
+    return SBR_OK;
+}
+
+int sbr_sweep_econ_dev(sbr_ctx* c, void* stream, const double* beta, const double* eta, const double* t_end,
+                       double x0, const double* u, int64_t n_beta, int64_t n_u, const double* p, int64_t n_p,
+                       const double* lambda, int64_t n_lambda, const double* kappa, int64_t n_kappa,
+                       const sbr_opts* opts, sbr_result_soa* out)
+{
+    int rc = econ_checks(c, opts, x0, n_beta, n_u, n_p, n_lambda, n_kappa);
+    if (rc) return rc;
+    SBR_SINGLE_DEVICE(c);
+    if (!beta || !eta || !t_end || !u || !p || !lambda || !kappa || !out || !out->xi || !out->tau_in_unc ||
+        !out->tau_out_unc || !out->aw_max || !out->tol || !out->status)
+        return fail(c, SBR_EARG, "null array");
+    if (hipSetDevice(c->device) != hipSuccess) return fail(c, SBR_EDEVICE, "hipSetDevice");
+    const sbr_opts o = resolve(opts);
+    sbr::ResultSoA r{out->xi, out->tau_in_unc, out->tau_out_unc, out->aw_max, out->tol, out->status, out->iters};
+    return fenced(c, stream, true, [&](hipStream_t s) {
+        return run_econ(c, s, beta, eta, t_end, x0, u, n_beta, n_u, p, n_p, lambda, n_lambda, kappa, n_kappa, o, r);
+    });
+}
+
+int sbr_sweep_econ(sbr_ctx* c, const double* beta, const double* eta, const double* t_end, double x0,
+                   const double* u, int64_t n_beta, int64_t n_u, const double* p, int64_t n_p, const double* lambda,
+                   int64_t n_lambda, const double* kappa, int64_t n_kappa, const sbr_opts* opts, sbr_result_soa* out)
+{
+    int rc = econ_checks(c, opts, x0, n_beta, n_u, n_p, n_lambda, n_kappa);
+    if (rc) return rc;
+    if (!beta || !eta || !t_end || !u || !p || !lambda || !kappa || !out) return fail(c, SBR_EARG, "null array");
+    for (int64_t i = 0; i < n_beta; i++)
+        if (!(beta[i] > 0.0) || !(t_end[i] > 0.0) || !(eta[i] > 0.0))
+            return fail(c, SBR_EARG, "ArgumentError: beta/eta/t_end must be positive");
+    for (int64_t j = 0; j < n_u; j++)
+        if (!(u[j] >= 0.0)) return fail(c, SBR_EARG, "ArgumentError: u must be non-negative");
+    for (int64_t a = 0; a < n_p; a++)
+        if (!(p[a] >= 0.0 && p[a] <= 1.0)) return fail(c, SBR_EARG, "ArgumentError: p must be in [0, 1]");
+    for (int64_t b = 0; b < n_lambda; b++)
+        if (!(lambda[b] > 0.0)) return fail(c, SBR_EARG, "ArgumentError: lambda must be positive");
+    for (int64_t k = 0; k < n_kappa; k++)
+        if (!(kappa[k] > 0.0 && kappa[k] < 1.0)) return fail(c, SBR_EARG, "ArgumentError: kappa must be in (0, 1)");
+    const sbr_opts o = resolve(opts);
+    const int64_t n_line = n_beta * n_p * n_lambda * n_kappa;
+    if (c->multi)
+        return multi_sweep_econ(c, beta, eta, t_end, x0, u, n_beta, n_u, p, n_p, lambda, n_lambda, kappa, n_kappa, o,
+                                out);
+    if (hipSetDevice(c->device) != hipSuccess) return fail(c, SBR_EDEVICE, "hipSetDevice");
+    const size_t np = (size_t)n_line * (size_t)n_u;
+    const size_t n_in = 3 * (size_t)n_beta + (size_t)(n_u + n_p + n_lambda + n_kappa);
+    const size_t in_bytes = n_in * 8;
+    const size_t out_bytes = np * (5 * 8 + 4 + 4);
+    rc = ensure_stage(c, in_bytes + out_bytes + 256);
+    if (rc) return rc;
+    char* base = (char*)c->stage;
+    double* dbeta = (double*)base;
+    double* deta = dbeta + n_beta;
+    double* dtend = deta + n_beta;
+    double* du = dtend + n_beta;
+    double* dp = du + n_u;
+    double* dlam = dp + n_p;
+    double* dkap = dlam + n_lambda;
+    double* dres = (double*)(base + ((in_bytes + 255) & ~(size_t)255));
+    sbr::ResultSoA r{dres, dres + np, dres + 2 * np, dres + 3 * np, dres + 4 * np, (uint32_t*)(dres + 5 * np),
+                     (int32_t*)((uint32_t*)(dres + 5 * np) + np)};
+    rc = ensure_res_pin(c, out_bytes);
+    if (rc) return rc;
+    return fenced(c, nullptr, false, [&](hipStream_t s) -> int {
+        const double* hin[7] = {beta, eta, t_end, u, p, lambda, kappa};
+        double* din[7] = {dbeta, deta, dtend, du, dp, dlam, dkap};
+        const int64_t nin[7] = {n_beta, n_beta, n_beta, n_u, n_p, n_lambda, n_kappa};
+        for (int k = 0; k < 7; k++)
+            HIP_TRY(c, hipMemcpyAsync(din[k], hin[k], (size_t)nin[k] * 8, hipMemcpyHostToDevice, s), SBR_EDEVICE);
+        int rc2 = run_econ(c, s, dbeta, deta, dtend, x0, du, n_beta, n_u, dp, n_p, dlam, n_lambda, dkap, n_kappa, o, r);
+        if (rc2) return rc2;
+        // one DMA copy of the contiguous result block into pinned memory, then the fields into
+        // the caller's arrays on several host threads (nothing is written before the sync succeeds)
+        const size_t blk = np * (5 * 8 + 4 + (out->iters ? 4 : 0));
+        HIP_TRY(c, hipMemcpyAsync(c->res_pin, dres, blk, hipMemcpyDeviceToHost, s), SBR_EDEVICE);
+        HIP_TRY(c, hipStreamSynchronize(s), SBR_EDEVICE);
+        const char* P = (const char*)c->res_pin;
+        std::vector<std::array<size_t, 3>> pieces;
+        double* hs[5] = {out->xi, out->tau_in_unc, out->tau_out_unc, out->aw_max, out->tol};
+        for (int k = 0; k < 5; k++)
+            if (hs[k]) pieces.push_back({(size_t)hs[k], (size_t)(P + (size_t)k * np * 8), np * 8});
+        if (out->status) pieces.push_back({(size_t)out->status, (size_t)(P + 5 * np * 8), np * 4});
+        if (out->iters) pieces.push_back({(size_t)out->iters, (size_t)(P + 5 * np * 8 + np * 4), np * 4});
+        sbr_host::parallel_copy(pieces);
+        if (o.early_exit_nan_run > 0 && out->status && out->xi && out->aw_max && out->tol)
+            sbr_apply_early_exit(n_line, n_u, o.early_exit_nan_run, out);
+        return SBR_OK;
+    });
+}
+
+int sbr_set_econ_workspace(sbr_ctx* c, int64_t bytes)
+{
+    if (!c || bytes < 0) return SBR_EARG;
+    if (c->multi) { // every rank's own budget
+        for (int r = 0; r < sbr_multi_impl::size(c->multi); r++) sbr_multi_impl::child(c->multi, r)->ec_budget = bytes;
+        return SBR_OK;
+    }
+    c->ec_budget = bytes;
     return SBR_OK;
 }
 
@@ -2988,6 +3192,46 @@ int multi_solve_points(sbr_ctx* c, const double* beta, const double* eta, const 
     int rc = sbr_multi_impl::run_sharded(c->multi, n, 1, fs, (size_t)(7 * cmax) * 8, stage, run,
                                          (o.flags & SBR_FLAG_RCCL_GATHER) != 0);
     return rc ? fail(c, rc, sbr_multi_impl::last_error(c->multi)) : SBR_OK;
+}
+
+// β × p × λ × κ × u: column i to rank i mod N with its n_p·n_lambda·n_kappa·n_u points, the four
+// axes to every rank
+int multi_sweep_econ(sbr_ctx* c, const double* beta, const double* eta, const double* t_end, double x0,
+                     const double* u, int64_t n_beta, int64_t n_u, const double* p, int64_t n_p, const double* lambda,
+                     int64_t n_lambda, const double* kappa, int64_t n_kappa, const sbr_opts& o, sbr_result_soa* out)
+{
+    const int N = sbr_multi_impl::size(c->multi);
+    const int64_t cmax = (n_beta + N - 1) / N;
+    const int64_t n_ax = n_u + n_p + n_lambda + n_kappa, per_col = n_p * n_lambda * n_kappa * n_u;
+    std::vector<FieldSpec> fs = {{out->xi, 8, 1},  {out->tau_in_unc, 8, 1}, {out->tau_out_unc, 8, 1},
+                                 {out->aw_max, 8, 1}, {out->tol, 8, 1},      {out->status, 4, 1},
+                                 {out->iters, 4, 1}};
+    auto stage = [&](int r, int64_t nc, void* in, hipStream_t) -> int {
+        std::vector<double> h(3 * nc + n_ax);
+        gather_cols(beta, 1, r, N, nc, h.data());
+        gather_cols(eta, 1, r, N, nc, h.data() + nc);
+        gather_cols(t_end, 1, r, N, nc, h.data() + 2 * nc);
+        double* ax = h.data() + 3 * nc;
+        memcpy(ax, u, (size_t)n_u * 8);
+        memcpy(ax + n_u, p, (size_t)n_p * 8);
+        memcpy(ax + n_u + n_p, lambda, (size_t)n_lambda * 8);
+        memcpy(ax + n_u + n_p + n_lambda, kappa, (size_t)n_kappa * 8);
+        return stage_host(in, h);
+    };
+    auto run = [&](int, int64_t nc, sbr_ctx* kid, hipStream_t s, void* in, const std::vector<void*>& f) -> int {
+        const double* d = (const double*)in;
+        const double* ax = d + 3 * nc;
+        sbr_result_soa ro{(double*)f[0], (double*)f[1], (double*)f[2], (double*)f[3], (double*)f[4],
+                          (uint32_t*)f[5], (int32_t*)f[6]};
+        return sbr_sweep_econ_dev(kid, s, d, d + nc, d + 2 * nc, x0, ax, nc, n_u, ax + n_u, n_p, ax + n_u + n_p,
+                                  n_lambda, ax + n_u + n_p + n_lambda, n_kappa, &o, &ro);
+    };
+    int rc = sbr_multi_impl::run_sharded(c->multi, n_beta, per_col, fs, (size_t)(3 * cmax + n_ax) * 8, stage, run,
+                                         (o.flags & SBR_FLAG_RCCL_GATHER) != 0);
+    if (rc) return fail(c, rc, sbr_multi_impl::last_error(c->multi));
+    if (o.early_exit_nan_run > 0 && out->status && out->xi && out->aw_max && out->tol)
+        sbr_apply_early_exit(n_beta * n_p * n_lambda * n_kappa, n_u, o.early_exit_nan_run, out);
+    return SBR_OK;
 }
 
 int multi_sweep_interest(sbr_ctx* c, const double* beta, const double* eta, const double* t_end, double x0,

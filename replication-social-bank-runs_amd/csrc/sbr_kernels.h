@@ -110,6 +110,21 @@ struct PointArgs {
     int32_t lds_cap;   // knots staged in LDS per array (3 arrays: t, G, HR); larger points run from global memory
 };
 
+// The economic-parameter sweep (sbr_econ.hip): the axes and one chunk of hazard classes.  Class
+// g = a·n_lam + b is the pair (p[a], lam[b]); the chunk holds classes [class0, class0 + n_class).
+// Row (k·n_beta + column) of hr, n_tau, n_le and status belongs to class class0 + k: every class has
+// its own hazard path, τ̄ counters and status word per column, so the classes of a column never
+// write the same word.
+struct EconArgs {
+    const double *p, *lam, *kappa; // the axes, in HBM
+    int32_t n_p, n_lam, n_kappa, n_u, n_beta;
+    int32_t class0, n_class;
+    double* hr;        // [n_class][n_beta][L.cap]
+    int32_t* n_tau;    // [n_class][n_beta]
+    int32_t* n_le;
+    uint32_t* status;
+};
+
 // Hetero learning output: t [n_col][cap], G [n_col][cap][K], hr/hrI [n_col][K][cap].
 struct HeteroBufs {
     double* t;
@@ -266,6 +281,15 @@ hipError_t launch_point_coop(const LearnBufs& L, const double* eta, const double
 // knots of row j come from launch_learn_kernel (la.fuse_hazard = 0) over pa.beta / eta / t_end.
 hipError_t launch_points(const LearnBufs& L, const LearnArgs& la, const PointArgs& pa, const ResultSoA& out,
                          int n_points, hipStream_t s);
+// sbr_sweep_econ, one chunk of classes.  launch_hazard_econ: one workgroup per (column, class of
+// the chunk) runs hazard_rate on the column's knots (rows of L from launch_learn_kernel with
+// la.fuse_hazard = 0) with the class's p, λ into the class's rows of e.  launch_equilibrium_econ:
+// the κ × u plane of every (column, class) — point j is (kappa[j / n_u], u[j % n_u]) — in tiles of
+// EQ_TILE points, results at ((column·n_p·n_lam + class)·n_kappa·n_u + j); a.n_u, a.kappa are ignored.
+hipError_t launch_hazard_econ(const double* beta, const double* eta, const LearnArgs& la, const LearnBufs& L,
+                              const EconArgs& e, hipStream_t s);
+hipError_t launch_equilibrium_econ(const LearnBufs& L, const double* eta, const double* t_end, const double* u,
+                                   const EqArgs& a, const EconArgs& e, const ResultSoA& out, hipStream_t s);
 // hazard_rate (solver.jl:153-185) of n_beta columns whose knots, n_knots, n_le (#knots <= η) and
 // status are in L (the hazard stage of launch_learn_logistic on its own)
 hipError_t launch_hazard(const double* beta, const double* eta, const LearnArgs& a, const LearnBufs& L, int n_beta,

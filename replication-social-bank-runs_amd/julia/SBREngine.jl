@@ -145,6 +145,43 @@ function solve_points(ctx::Context, β, u; η = 15.0, tspan_end = 30.0, p = 0.5,
 end
 
 """
+    sweep_econ(ctx, β_vals, u_vals; p, κ, λ, η, tspan_end, x0, early_exit = 0)
+
+Comparative statics in every economic parameter at once: the product β × p × λ × κ × u with
+`lr = solve_learning(...)` once per β and `solve_equilibrium_baseline(lr, EconomicParameters(u, p,
+κ, λ, η_bar, η))` per combination (scripts/1_baseline.jl:44, 169).  `p`, `κ`, `λ` are vectors or
+scalars (a scalar is an axis of length 1); `η`/`tspan_end` are per-β (scalars broadcast).  Returns
+`(max_AW, ξ, τ̄_IN, τ̄_OUT, tolerance, status)` as arrays indexed `[u, κ, λ, p, β]` (Julia's
+column-major view of the library's u-fastest layout); `[:, c, b, a, :]` is
+`solve_equilibrium_grid` at `(p[a], κ[c], λ[b])`.  `early_exit` applies the 5-NaN rule along every
+u-line.
+"""
+function sweep_econ(ctx::Context, β_vals, u_vals; p = 0.5, κ = 0.6, λ = 0.01, η = 15.0, tspan_end = 30.0,
+                    x0 = 1e-4, early_exit = 0)
+    β = collect(Float64, β_vals); u = collect(Float64, u_vals)
+    axis(x) = x isa Number ? Float64[x] : collect(Float64, x)
+    pv = axis(p); κv = axis(κ); λv = axis(λ)
+    nb, nu, np, nk, nl = length(β), length(u), length(pv), length(κv), length(λv)
+    col(x) = x isa Number ? fill(Float64(x), nb) : collect(Float64, x)
+    ηv = col(η); tv = col(tspan_end)
+    (length(ηv) == nb && length(tv) == nb) ||
+        throw(ArgumentError("sweep_econ: η and tspan_end need length(β) = $nb entries"))
+    xi = Array{Float64}(undef, nu, nk, nl, np, nb); tin = similar(xi); tout = similar(xi)
+    aw = similar(xi); tol = similar(xi); st = Array{UInt32}(undef, nu, nk, nl, np, nb)
+    opts = Ref(Opts(; early_exit))
+    GC.@preserve β u pv κv λv ηv tv xi tin tout aw tol st begin
+        soa = Ref(ResultSoA(pointer(xi), pointer(tin), pointer(tout), pointer(aw), pointer(tol), pointer(st),
+                            Ptr{Int32}(C_NULL)))
+        rc = ccall((:sbr_sweep_econ, libsbr), Cint,
+                   (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Float64, Ptr{Float64}, Int64, Int64,
+                    Ptr{Float64}, Int64, Ptr{Float64}, Int64, Ptr{Float64}, Int64, Ref{Opts}, Ref{ResultSoA}),
+                   ctx.ptr, β, ηv, tv, x0, u, nb, nu, pv, np, λv, nl, κv, nk, opts, soa)
+        check(ctx, rc)
+    end
+    return (max_AW = aw, ξ = xi, τ_bar_IN_UNC = tin, τ_bar_OUT_UNC = tout, tolerance = tol, status = st)
+end
+
+"""
     learn(ctx, β, tspan_end, x0; cap = 1 << 16)
 
 `solve_SIhomogeneous` (learning.jl:41-54) on the GPU: the knot grid `t` and CDF values `G`

@@ -11,7 +11,10 @@ from .engine import (  # noqa: F401
     LearningResults,
     LinearInterpolation,
     SolvedModel,
+    comparative_statics,
     default_engine,
+    econ_axes,
+    econ_from_model,
     get_AW_functions,
     SolvedModelHetero,
     SolvedModelInterest,

@@ -95,6 +95,10 @@ _SIGS = {
     "sbr_solve_points": (ctypes.c_int, [_P, _P, _P, _P, _D, _P, _P, _P, _P, _I64, _P, _P]),
     "sbr_solve_points_dev": (ctypes.c_int, [_P, _P, _P, _P, _P, _D, _P, _P, _P, _P, _I64, _P, _P]),
     "sbr_set_points_workspace": (ctypes.c_int, [_P, _I64]),
+    "sbr_sweep_econ": (ctypes.c_int, [_P, _P, _P, _P, _D, _P, _I64, _I64, _P, _I64, _P, _I64, _P, _I64, _P, _P]),
+    "sbr_sweep_econ_dev": (ctypes.c_int, [_P, _P, _P, _P, _P, _D, _P, _I64, _I64, _P, _I64, _P, _I64, _P, _I64, _P,
+                                          _P]),
+    "sbr_set_econ_workspace": (ctypes.c_int, [_P, _I64]),
     "sbr_batch_wait": (ctypes.c_int, [_P, _P, _I64]),
     "sbr_batch_reserve": (ctypes.c_int, [_P, _I64, _I64, _P]),
     "sbr_set_batch_workspace": (ctypes.c_int, [_P, _I64]),

@@ -286,6 +286,61 @@ class Engine:
         free HBM); a list that needs more runs in chunks (sbr_set_points_workspace)."""
         check(self._L.sbr_set_points_workspace(self._ctx, int(nbytes)), self._ctx, "sbr_set_points_workspace")
 
+    # ------------------------------------------------------------------ β × p × λ × κ × u
+    def sweep_econ(self, beta, eta, t_end, u, p, kappa, lam, x0=1e-4, early_exit: int = 0, max_iters: int = 100,
+                   knot_capacity: int = 65536, exhaustive: bool = False, flags: int = 0, out: dict | None = None,
+                   ode_rtol: float | None = None, ode_atol: float | None = None,
+                   ode_maxiters: int | None = None) -> dict:
+        """The product of the five axes in one call, each β learned once (sbr_sweep_econ).  ``eta``
+        and ``t_end`` are per column (scalars are repeated); ``u``, ``p``, ``kappa``, ``lam`` are
+        arrays or scalars, a scalar being an axis of length 1.  Returns arrays shaped
+        (n_beta, n_p, n_lam, n_kappa, n_u); the line [i, a, b, c, :] is row i of
+        ``sweep_baseline`` at (p[a], kappa[c], lam[b]).  ``early_exit`` applies the reference's
+        consecutive-no-run rule along every u-line.  ``out``: the caller's result arrays as in
+        ``sweep_baseline``."""
+        ax = econ_axes(beta, eta, t_end, u, p, kappa, lam)
+        shape = tuple(ax[k].size for k in ("beta", "p", "lam", "kappa", "u"))
+        n = int(np.prod(shape))
+        if out is None:
+            out = {k: np.empty(n) for k in RESULT_FIELDS}
+            out["status"] = np.empty(n, np.uint32)
+            out["iters"] = np.empty(n, np.int32)
+        else:
+            out = host_result_views(out, n)
+        soa = _lib.ResultSoA(*[_ptr(out[k]) for k in (*RESULT_FIELDS, "status", "iters")])
+        opts = _opts(ode_rtol, ode_atol, ode_maxiters, early_exit_nan_run=early_exit, bisect_max_iters=max_iters,
+                     knot_capacity=knot_capacity, flags=flags | (_lib.SBR_FLAG_EXHAUSTIVE if exhaustive else 0))
+        rc = self._L.sbr_sweep_econ(self._ctx, _ptr(ax["beta"]), _ptr(ax["eta"]), _ptr(ax["t_end"]), float(x0),
+                                    _ptr(ax["u"]), shape[0], shape[4], _ptr(ax["p"]), shape[1], _ptr(ax["lam"]),
+                                    shape[2], _ptr(ax["kappa"]), shape[3], ctypes.byref(opts), ctypes.byref(soa))
+        check(rc, self._ctx, "sbr_sweep_econ")
+        return {k: (v.reshape(shape) if v is not None else None) for k, v in out.items()}
+
+    def sweep_econ_dev(self, beta, eta, t_end, u, p, kappa, lam, x0, out: dict, stream: int | None = None,
+                       max_iters: int = 100, knot_capacity: int = 65536, exhaustive: bool = False, flags: int = 0,
+                       ode_rtol: float | None = None, ode_atol: float | None = None,
+                       ode_maxiters: int | None = None):
+        """Device-pointer variant on torch tensors (float64 cuda; ``eta`` and ``t_end`` as long as
+        ``beta``, each axis a tensor of one element or more) — enqueue only, no host sync, no
+        early-exit pass.  ``out`` holds preallocated tensors as for ``sweep_baseline_dev``, each
+        with n_beta·n_p·n_lam·n_kappa·n_u elements.  A point whose own u, p, κ or λ breaks its rule
+        ends as SBR_ARG_INVALID."""
+        nb, nu, n_p, nl, nk = beta.numel(), u.numel(), p.numel(), lam.numel(), kappa.numel()
+        soa = _lib.ResultSoA(*_out_ptrs(out, (*RESULT_FIELDS, "status", "iters"), nb * n_p * nl * nk * nu,
+                                        required=(*RESULT_FIELDS, "status")))
+        opts = _opts(ode_rtol, ode_atol, ode_maxiters, early_exit_nan_run=0, bisect_max_iters=max_iters,
+                     knot_capacity=knot_capacity, flags=(_lib.SBR_FLAG_EXHAUSTIVE if exhaustive else 0) | flags)
+        rc = self._L.sbr_sweep_econ_dev(self._ctx, stream, _dptr(beta, "beta", _F64), _dptr(eta, "eta", _F64, nb),
+                                        _dptr(t_end, "t_end", _F64, nb), x0, _dptr(u, "u", _F64), nb, nu,
+                                        _dptr(p, "p", _F64), n_p, _dptr(lam, "lam", _F64), nl,
+                                        _dptr(kappa, "kappa", _F64), nk, ctypes.byref(opts), ctypes.byref(soa))
+        check(rc, self._ctx, "sbr_sweep_econ_dev")
+
+    def set_econ_workspace(self, nbytes: int):
+        """Budget in bytes for the workspace of ``sweep_econ`` (0 = the default, 40 % of free HBM);
+        it caps the hazard classes (p, λ) solved per chunk (sbr_set_econ_workspace)."""
+        check(self._L.sbr_set_econ_workspace(self._ctx, int(nbytes)), self._ctx, "sbr_set_econ_workspace")
+
     def learn_baseline(self, beta, eta, t_end, x0=1e-4, stop_after_eta=False, cap=65536, tol=None,
                        ode_maxiters: int | None = None):
         beta = np.ascontiguousarray(beta, np.float64)
@@ -819,6 +874,59 @@ def points_from_models(models) -> dict:
                 eta=col(lambda m: m.economic.eta), t_end=col(lambda m: m.learning.tspan[1]),
                 p=col(lambda m: m.economic.p), kappa=col(lambda m: m.economic.kappa),
                 lam=col(lambda m: m.economic.lam), x0=x0s.pop() if x0s else 1e-4)
+
+
+def econ_axes(beta, eta, t_end, u, p, kappa, lam) -> dict:
+    """The seven arrays ``Engine.sweep_econ`` hands to sbr_sweep_econ: ``beta`` one-dimensional
+    (a scalar is one column), ``eta`` and ``t_end`` broadcast to it, and each of ``u``, ``p``,
+    ``kappa``, ``lam`` a one-dimensional axis (a scalar is an axis of length 1).  Pure Python."""
+    b = np.atleast_1d(np.asarray(beta, np.float64))
+    ax = {"beta": b}
+    if b.ndim != 1:
+        raise ArgumentError("beta: a scalar or a one-dimensional array")
+    for name, v in (("eta", eta), ("t_end", t_end)):
+        try:
+            ax[name] = np.broadcast_to(np.asarray(v, np.float64), b.shape)
+        except ValueError:
+            raise ArgumentError(f"{name}: a scalar or one value per beta") from None
+    for name, v in (("u", u), ("p", p), ("kappa", kappa), ("lam", lam)):
+        a = np.atleast_1d(np.asarray(v, np.float64))
+        if a.ndim != 1:
+            raise ArgumentError(f"{name}: a scalar or a one-dimensional array")
+        ax[name] = a
+    return {k: np.ascontiguousarray(v) for k, v in ax.items()}
+
+
+_ECON_AXES = ("u", "p", "kappa", "lam")
+
+
+def econ_from_model(model: ModelParameters, **axes) -> dict:
+    """The arguments of ``Engine.sweep_econ`` for a sweep of ``axes`` (any of ``u``, ``p``,
+    ``kappa``, ``lam``) around one ``ModelParameters``: every value that is not swept is the
+    model's own, η and tspan the model's already resolved ones, so the copy-modify carry-over
+    (model.jl:189-211) is whatever the caller built — as in ``points_from_models``.
+    ArgumentError for an axis of another name or a tspan that does not start at 0."""
+    if not isinstance(model, ModelParameters):
+        raise ArgumentError("comparative_statics takes ModelParameters")
+    unknown = sorted(set(axes) - set(_ECON_AXES))
+    if unknown:
+        raise ArgumentError(f"unknown axis {unknown}: the axes are {list(_ECON_AXES)}")
+    if model.learning.tspan[0] != 0.0:
+        raise ArgumentError("the engine integrates from t = 0 (every reference call site does)")
+    e = model.economic
+    own = dict(u=e.u, p=e.p, kappa=e.kappa, lam=e.lam)
+    return dict(beta=model.learning.beta, eta=e.eta, t_end=model.learning.tspan[1], x0=model.learning.x0,
+                **{k: (axes[k] if axes.get(k) is not None else own[k]) for k in _ECON_AXES})
+
+
+def comparative_statics(model: ModelParameters, engine: Engine | None = None, **axes) -> dict:
+    """Comparative statics in the economic parameters around one model: the axes ``u``, ``p``,
+    ``kappa``, ``lam`` given are swept (arrays), the others stay the model's, and the learning ODE
+    is solved once (``Engine.sweep_econ``).  Returns arrays shaped (n_p, n_lam, n_kappa, n_u), an
+    axis that is not swept having length 1."""
+    args = econ_from_model(model, **axes)  # an unknown axis raises before an engine is looked for
+    r = (engine or default_engine()).sweep_econ(**args)
+    return {k: (v[0] if v is not None else None) for k, v in r.items()}
 
 
 def solve_models(models, engine: Engine | None = None) -> dict:
