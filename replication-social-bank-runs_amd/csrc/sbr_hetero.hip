@@ -521,7 +521,7 @@ __device__ __forceinline__ void solve_hetero_point(const HCol<K, PT>& C, const d
 }
 
 constexpr int kHetBlock = 256; // u points per hetero equilibrium workgroup (512 was slower)
-constexpr int kHetMinW = 2; // waves per SIMD: two 4-wave workgroups per CU (LDS slab: kHetLds in sbr_capi.hip)
+constexpr int kHetMinW = 2; // waves per SIMD: two 4-wave workgroups per CU (LDS slab: kHetLds in sbr_ctx.h)
 template <int K, int BLOCK, int MODE>
 __global__ __launch_bounds__(BLOCK, kHetMinW)
 void equilibrium_hetero_kernel(HeteroBufs L, const double* __restrict__ dist,

@@ -77,7 +77,7 @@ def test_slab_overflow_runs_from_global_memory(engine, oracle):
     g = sbr.hetero_config4(2, 4, 12)
     t, G, _ = learned(2, 4, 12, 1)
     tm, Gm = refined(t, G)
-    slab = min(3 * engine.device_info()["lds_knot_capacity"], 10176)  # het_lds() of sbr_capi.hip
+    slab = min(3 * engine.device_info()["lds_knot_capacity"], 10176)  # het_lds() of sbr_ctx.h
     assert len(t) <= slab < len(tm)
     args = (g.betas[1], g.dist, g.eta[1], g.t_end[1])
     u = np.array([0.02, 0.05, 0.3, 0.9])
