@@ -533,6 +533,46 @@ int sbr_sweep_interest_dev(sbr_ctx* ctx, void* stream, const double* beta, const
                            double lambda, double r, double delta, const sbr_opts* opts, sbr_result_soa* out,
                            int64_t* rk_steps);
 
+/*
+ * The interest-rate extension in every economic parameter at once — β × p × λ × (r, δ) × κ × u,
+ * learning each β once and integrating each value function once:
+ *     lr = solve_learning(LearningParameters(beta[i], (0, t_end[i]), x0))            once per column
+ *     solve_equilibrium_interest(lr, econ(u[j], p[a], kappa[c], lambda[b], r[d], delta[d]), model)
+ * The learning solve depends on (β, t_end, x0) only, the hazard path on (column, η, p, λ), the value
+ * function V and the buffers τ̄_IN, τ̄_OUT taken from h − rV > u on (HR, r, δ, u); κ enters only
+ * compute_ξ and the AW pass (interest_rate_solver.jl:51-150).  So one value function serves every κ.
+ * The rates are a list of n_rate pairs (r[d], delta[d]), not two axes: 0 <= r < δ couples them.
+ * Every out field has n_beta·n_p·n_lambda·n_rate·n_kappa·n_u entries (iters may be NULL), element
+ * (i, a, b, d, c, j) at (((((i·n_p + a)·n_lambda + b)·n_rate + d)·n_kappa + c)·n_u + j).  The line
+ * [i, a, b, d, c, :] is exactly row i of sbr_sweep_interest(beta, eta, t_end, x0, u, …, p[a],
+ * kappa[c], lambda[b], r[d], delta[d], opts): all seven fields and the status bits, the learning
+ * and the value-function bits included, at any tolerances and caps; a pair with r[d] = 0 gives the
+ * baseline rows.  rk_steps (may be NULL) has no κ axis: n_beta·n_p·n_lambda·n_rate·n_u entries,
+ * element (i, a, b, d, j) = the sweep's rk_steps[i, j] at any κ — V is integrated once per (column,
+ * class, rate, u).  No early-exit post-pass, as in sbr_sweep_interest.
+ * SBR_EARG as sbr_sweep_econ, and for a pair that breaks r >= 0, δ > 0, r < δ (a NaN breaks it),
+ * n_rate <= 0, n_rate·n_u > 2^30, more than 2^40 results in all, or more than 65,535 columns on one
+ * device.  Host pointers; synchronous; a failed call writes none of the
+ * caller's arrays.  SBR_FLAG_EXHAUSTIVE is honoured.  On an n-device context the columns are dealt
+ * cyclically, over either transport.  Workspace and chunking are sbr_sweep_econ's
+ * (sbr_set_econ_workspace); the results do not depend on the chunking.
+ */
+int sbr_sweep_interest_econ(sbr_ctx* ctx, const double* beta, const double* eta, const double* t_end, double x0,
+                            const double* u, int64_t n_beta, int64_t n_u, const double* p, int64_t n_p,
+                            const double* lambda, int64_t n_lambda, const double* r, const double* delta,
+                            int64_t n_rate, const double* kappa, int64_t n_kappa, const sbr_opts* opts,
+                            sbr_result_soa* out, int64_t* rk_steps);
+/* Same on device pointers (the nine arrays, every out field and rk_steps in HBM), enqueued on
+ * `stream`; no host synchronisation.  The axes cannot be read on the host: a point whose own u, p,
+ * λ, κ or rate pair breaks its rule ends with status == SBR_ARG_INVALID, ξ = τ̄_IN = τ̄_OUT = AW_max =
+ * NaN, tol = Inf, iters = 0 (as in sbr_solve_points), rk_steps = 0 where u, p, λ or the pair is at
+ * fault, and no other point is touched.  Needs a single-device context. */
+int sbr_sweep_interest_econ_dev(sbr_ctx* ctx, void* stream, const double* beta, const double* eta,
+                                const double* t_end, double x0, const double* u, int64_t n_beta, int64_t n_u,
+                                const double* p, int64_t n_p, const double* lambda, int64_t n_lambda,
+                                const double* r, const double* delta, int64_t n_rate, const double* kappa,
+                                int64_t n_kappa, const sbr_opts* opts, sbr_result_soa* out, int64_t* rk_steps);
+
 /* One interest-rate equilibrium with the paths scripts/3_interest_rates.jl
  * plots (value_function.pdf, hazard_decomposition.pdf): τ̄ grid and HR (n_tau),
  * V on that grid (n_v; 0 when r = 0, fewer than n_tau if the value-function

@@ -1,6 +1,7 @@
 // sbr_capi_baseline.hip — the baseline model's entry points of the C API: the learning workspaces,
 // single sweeps (chunked and readiness schedules), the pipelined batch, lists of models
-// (sbr_solve_points), β × p × λ × κ × u (sbr_sweep_econ) and the interest-rate extension.
+// (sbr_solve_points), β × p × λ × κ × u (sbr_sweep_econ), the interest-rate extension and its product
+// with the economic parameters (sbr_sweep_interest_econ).
 #include "sbr_hostio.h"
 
 using namespace sbr_capi;
@@ -417,9 +418,18 @@ size_t econ_class_bytes(size_t cap) { return cap * sizeof(double) + 3 * sizeof(i
 // equilibrium launches over the κ × u planes.  A chunk's hazards start after the previous
 // chunk's equilibria (they share the class rows); no host synchronisation.  Timing records:
 // kind 0 = the learning launch, kind 1 = the hazard and equilibrium launches.
+// With `rates` (sbr_sweep_interest_econ) the equilibrium launches are the interest-rate model's over
+// the rate × u planes, every κ solved on one value function (sbr_interest_econ.hip); out then has a
+// rate axis outside κ.
+struct RateAxis {
+    const double *r, *delta; // n pairs, on the device
+    int64_t n;
+    int64_t* steps;          // value-function steps, no κ axis (may be null)
+};
 int run_econ(sbr_ctx* c, hipStream_t s, const double* beta, const double* eta, const double* t_end, double x0,
              const double* u, int64_t n_beta, int64_t n_u, const double* p, int64_t n_p, const double* lambda,
-             int64_t n_lambda, const double* kappa, int64_t n_kappa, const sbr_opts& o, const sbr::ResultSoA& out)
+             int64_t n_lambda, const double* kappa, int64_t n_kappa, const sbr_opts& o, const sbr::ResultSoA& out,
+             const RateAxis* rates = nullptr)
 {
     const size_t cap = (size_t)o.knot_capacity;
     const int64_t n_class = n_p * n_lambda;
@@ -450,8 +460,12 @@ int run_econ(sbr_ctx* c, hipStream_t s, const double* beta, const double* eta, c
     hipEvent_t t0 = tstart(c, s);
     HIP_TRY(c, sbr::launch_learn_kernel(beta, eta, t_end, la, L, s, 1), SBR_EDEVICE);
     tend(c, s, 0, t0);
-    sbr::EqArgs ea{0.0, (int32_t)(n_kappa * n_u), o.bisect_max_iters, c->lds_cap_b, nullptr,
+    // (the interest slab stages HR too: its knot capacity is the three-array one, as in run_interest)
+    sbr::EqArgs ea{0.0, (int32_t)(n_kappa * n_u), o.bisect_max_iters, rates ? c->lds_cap : c->lds_cap_b, nullptr,
                    (o.flags & SBR_FLAG_EXHAUSTIVE) ? 1 : 0, (o.flags >> 8) & 0x17};
+    const sbr::InterestEconArgs ie{rates ? rates->r : nullptr, rates ? rates->delta : nullptr,
+                                   (int32_t)(rates ? rates->n : 0), o.ode_reltol, o.ode_abstol, o.ode_maxiters,
+                                   rates ? rates->steps : nullptr};
     t0 = tstart(c, s);
     int launches = 0;
     for (int64_t g0 = 0; g0 < n_class; g0 += per) {
@@ -461,7 +475,8 @@ int run_econ(sbr_ctx* c, hipStream_t s, const double* beta, const double* eta, c
                               (int32_t)n_beta, (int32_t)g0, (int32_t)ng, c->ec_hr, c->ec_cnt, c->ec_cnt + rows,
                               (uint32_t*)(c->ec_cnt + 2 * rows)};
         HIP_TRY(c, sbr::launch_hazard_econ(beta, eta, la, L, e, s), SBR_EDEVICE);
-        HIP_TRY(c, sbr::launch_equilibrium_econ(L, eta, t_end, u, ea, e, out, s), SBR_EDEVICE);
+        if (rates) HIP_TRY(c, sbr::launch_interest_econ(L, eta, t_end, u, ea, e, ie, out, s), SBR_EDEVICE);
+        else HIP_TRY(c, sbr::launch_equilibrium_econ(L, eta, t_end, u, ea, e, out, s), SBR_EDEVICE);
         launches += 3;
     }
     tend(c, s, 1, t0, launches);
@@ -977,6 +992,118 @@ int sbr_sweep_interest(sbr_ctx* c, const double* beta, const double* eta, const 
         if (!rc) rc = copy_out(c, s, {{rk_steps, dsteps, np * 8}});
         if (rc) return rc;
         HIP_TRY(c, hipStreamSynchronize(s), SBR_EDEVICE);
+        return SBR_OK;
+    });
+}
+
+// the checks sbr_sweep_interest_econ and sbr_sweep_interest_econ_dev share, before any array is looked at
+static int interest_econ_checks(sbr_ctx* c, const sbr_opts* opts, double x0, int64_t n_beta, int64_t n_u,
+                                int64_t n_p, int64_t n_lambda, int64_t n_rate, int64_t n_kappa)
+{
+    if (int rc = econ_checks(c, opts, x0, n_beta, n_u, n_p, n_lambda, n_kappa)) return rc;
+    const int64_t lim = 1 << 30;
+    if (n_rate <= 0 || n_rate > lim || n_rate * n_u > lim) return fail(c, SBR_EARG, "grid size");
+    // at most 2^40 results in all, so that no index of the call can wrap: each factor is within 2^30,
+    // and the quotients keep every intermediate product below 2^61
+    const int64_t total = (int64_t)1 << 40, plane = n_rate * n_u, per_col = n_p * n_lambda;
+    if (plane > total / n_kappa || per_col > total / (plane * n_kappa) || n_beta > total / (plane * n_kappa * per_col))
+        return fail(c, SBR_EARG, "grid size: more than 2^40 points");
+    return SBR_OK;
+}
+
+// one device's launch takes a column per grid row (launch_hazard_econ, launch_interest_econ)
+static int interest_econ_cols(sbr_ctx* c, int64_t n_beta)
+{
+    return n_beta > 65535 ? fail(c, SBR_EARG, "grid size: more than 65,535 columns on one device") : SBR_OK;
+}
+
+int sbr_sweep_interest_econ_dev(sbr_ctx* c, void* stream, const double* beta, const double* eta, const double* t_end,
+                                double x0, const double* u, int64_t n_beta, int64_t n_u, const double* p,
+                                int64_t n_p, const double* lambda, int64_t n_lambda, const double* r,
+                                const double* delta, int64_t n_rate, const double* kappa, int64_t n_kappa,
+                                const sbr_opts* opts, sbr_result_soa* out, int64_t* rk_steps)
+{
+    int rc = interest_econ_checks(c, opts, x0, n_beta, n_u, n_p, n_lambda, n_rate, n_kappa);
+    if (rc) return rc;
+    SBR_SINGLE_DEVICE(c);
+    if ((rc = interest_econ_cols(c, n_beta))) return rc;
+    if (!beta || !eta || !t_end || !u || !p || !lambda || !r || !delta || !kappa || !has_fields(out))
+        return fail(c, SBR_EARG, "null array");
+    if (hipSetDevice(c->device) != hipSuccess) return fail(c, SBR_EDEVICE, "hipSetDevice");
+    const sbr_opts o = resolve(opts);
+    const sbr::ResultSoA rs = device_soa(out);
+    const RateAxis rates{r, delta, n_rate, rk_steps};
+    return fenced(c, stream, true, [&](hipStream_t s) {
+        return run_econ(c, s, beta, eta, t_end, x0, u, n_beta, n_u, p, n_p, lambda, n_lambda, kappa, n_kappa, o, rs,
+                        &rates);
+    });
+}
+
+// β × p × λ × (r, δ) × κ × u on n devices: column i to rank i mod N with its n_p·n_lambda·n_rate·n_u
+// shard points of n_kappa results and one step count each, the five axes to every rank
+static int multi_sweep_interest_econ(sbr_ctx* c, const Inputs& in, double x0, int64_t n_beta, int64_t n_u,
+                                     int64_t n_p, int64_t n_lambda, int64_t n_rate, int64_t n_kappa,
+                                     const sbr_opts& o, sbr_result_soa* out, int64_t* rk_steps)
+{
+    std::vector<FieldSpec> fs = result_fields(out);
+    for (FieldSpec& f : fs) f.per_pt = (size_t)n_kappa;
+    fs.push_back({rk_steps, 8, 1});
+    auto run = [&](sbr_ctx* kid, hipStream_t s, int64_t nc, const DevInputs& d, const std::vector<void*>& f) -> int {
+        sbr_result_soa ro = rank_results(f);
+        return sbr_sweep_interest_econ_dev(kid, s, d[0], d[1], d[2], x0, d[3], nc, n_u, d[4], n_p, d[5], n_lambda,
+                                           d[6], d[7], n_rate, d[8], n_kappa, &o, &ro, (int64_t*)f[7]);
+    };
+    return fan_out(c, in, n_beta, n_p * n_lambda * n_rate * n_u, fs, o, run);
+}
+
+int sbr_sweep_interest_econ(sbr_ctx* c, const double* beta, const double* eta, const double* t_end, double x0,
+                            const double* u, int64_t n_beta, int64_t n_u, const double* p, int64_t n_p,
+                            const double* lambda, int64_t n_lambda, const double* r, const double* delta,
+                            int64_t n_rate, const double* kappa, int64_t n_kappa, const sbr_opts* opts,
+                            sbr_result_soa* out, int64_t* rk_steps)
+{
+    int rc = interest_econ_checks(c, opts, x0, n_beta, n_u, n_p, n_lambda, n_rate, n_kappa);
+    if (rc) return rc;
+    if (!beta || !eta || !t_end || !u || !p || !lambda || !r || !delta || !kappa || !out)
+        return fail(c, SBR_EARG, "null array");
+    rc = check_positive(c, n_beta, {beta, t_end, eta}, "ArgumentError: beta/eta/t_end must be positive");
+    if (!rc) rc = check_u(c, u, n_u);
+    if (rc) return rc;
+    for (int64_t a = 0; a < n_p; a++)
+        if (!(p[a] >= 0.0 && p[a] <= 1.0)) return fail(c, SBR_EARG, "ArgumentError: p must be in [0, 1]");
+    rc = check_positive(c, n_lambda, {lambda}, "ArgumentError: lambda must be positive");
+    if (rc) return rc;
+    for (int64_t d = 0; d < n_rate; d++)
+        if (!interest_valid(r[d], delta[d])) return fail(c, SBR_EARG, "ArgumentError: need 0 <= r < delta");
+    for (int64_t k = 0; k < n_kappa; k++)
+        if (!(kappa[k] > 0.0 && kappa[k] < 1.0)) return fail(c, SBR_EARG, "ArgumentError: kappa must be in (0, 1)");
+    const sbr_opts o = resolve(opts);
+    const Inputs in{cols(beta), cols(eta), cols(t_end), shared(u, (size_t)n_u), shared(p, (size_t)n_p),
+                    shared(lambda, (size_t)n_lambda), shared(r, (size_t)n_rate), shared(delta, (size_t)n_rate),
+                    shared(kappa, (size_t)n_kappa)};
+    if (c->multi)
+        return multi_sweep_interest_econ(c, in, x0, n_beta, n_u, n_p, n_lambda, n_rate, n_kappa, o, out, rk_steps);
+    if ((rc = interest_econ_cols(c, n_beta))) return rc;
+    if (hipSetDevice(c->device) != hipSuccess) return fail(c, SBR_EDEVICE, "hipSetDevice");
+    // the result block of np points, then the step counts, one per value function
+    const size_t ns = (size_t)(n_beta * n_p * n_lambda * n_rate) * (size_t)n_u, np = ns * (size_t)n_kappa;
+    void* dres;
+    rc = ensure_io(c, in, (size_t)n_beta, result_bytes(np) + ns * 8, &dres);
+    if (!rc) rc = ensure_res_pin(c, result_bytes(np));
+    if (rc) return rc;
+    const auto d = in.dev(c->stage, (size_t)n_beta);
+    const sbr::ResultSoA rs = carve_results(dres, np);
+    int64_t* dsteps = (int64_t*)((char*)dres + result_bytes(np));
+    const RateAxis rates{d[6], d[7], n_rate, dsteps};
+    return fenced(c, nullptr, false, [&](hipStream_t s) -> int {
+        rc = in.stage(c, c->stage, (size_t)n_beta, s);
+        if (!rc) rc = run_econ(c, s, d[0], d[1], d[2], x0, d[3], n_beta, n_u, d[4], n_p, d[5], n_lambda, d[8], n_kappa, o, rs, &rates);
+        if (!rc) rc = readback_enqueue(c, dres, np, out->iters != nullptr, s);
+        if (rc) return rc;
+        // the step counts reach the caller only after the sweep itself has succeeded
+        HIP_TRY(c, hipStreamSynchronize(s), SBR_EDEVICE);
+        if (rk_steps) HIP_TRY(c, hipMemcpy(rk_steps, dsteps, ns * 8, hipMemcpyDeviceToHost), SBR_EDEVICE);
+        scatter_results(c->res_pin, np, out);
         return SBR_OK;
     });
 }

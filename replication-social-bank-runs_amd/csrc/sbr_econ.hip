@@ -18,6 +18,7 @@
 // A translation unit of its own: the sweep kernels' machine code (and with it the code hashes
 // bench.py keys its PMC counters on) does not depend on these kernels.
 #include "sbr_device.h"
+#include "sbr_econ_dev.h"
 #include "sbr_eq_dev.h"
 #include "sbr_hazard_dev.h"
 #include "sbr_kernels.h"
@@ -25,24 +26,6 @@
 #include "sbr_solve_dev.h"
 
 namespace sbr {
-
-// the learning buffers as class k of the chunk sees them: the column's knots, the class's rows
-__device__ __forceinline__ LearnBufs econ_class_bufs(const LearnBufs& L, const EconArgs& e, const int k)
-{
-    LearnBufs C = L;
-    const size_t r0 = (size_t)k * (size_t)e.n_beta;
-    C.hr = e.hr + r0 * (size_t)L.cap;
-    C.n_tau = e.n_tau + r0;
-    C.n_le = e.n_le + r0;
-    C.status = e.status + r0;
-    return C;
-}
-
-// EconomicParameters' rules for p and λ (model.jl:71-76); a NaN breaks its rule
-__device__ __forceinline__ bool econ_class_bad(const double p, const double lam)
-{
-    return !(p >= 0.0 && p <= 1.0) || !(lam > 0.0);
-}
 
 __global__ __launch_bounds__(HZ_BLOCK) void hazard_econ_kernel(const double* __restrict__ beta,
                                                                const double* __restrict__ eta, LearnArgs a,

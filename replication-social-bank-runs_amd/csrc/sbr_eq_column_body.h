@@ -4,6 +4,8 @@
 //   SBR_EQ_U(j), SBR_EQ_KAPPA(j)   the u and κ of point j
 //   SBR_EQ_BAD(uj, j)              the point's own ArgumentError (EconomicParameters, model.jl:71-76)
 //   SBR_EQ_OUT(b, j)               the index of its result
+// or, in place of the four, SBR_EQ_LANE(j): a statement that solves and stores everything lane j of
+// the tile stands for, on the body's locals (sbr_interest_econ.hip: one value function, every κ).
 // The β×u sweeps' expansion is the text eq_column had before the body was shared, token for
 // token, so their machine code does not depend on the other users.
 {
@@ -276,6 +278,9 @@
         if (j0 + base >= j1) break;
         const int j = j0 + base + lane;
         if (j >= j1) continue;
+#ifdef SBR_EQ_LANE
+        SBR_EQ_LANE(j);
+#else
         const double uj = SBR_EQ_U(j);
         PointResult r;
         int64_t vsteps = 0;
@@ -305,5 +310,6 @@
         out.tol[o] = r.tol;
         out.status[o] = r.status;
         if (out.iters) out.iters[o] = r.iters;
+#endif
     }
 }

@@ -554,6 +554,9 @@ struct SaveScan {
 
 // solve_equilibrium_interest (interest_rate_solver.jl:51-150) for one u with r > 0:
 // V on the HR grid, optimal_buffer on h − rV, then the baseline's compute_ξ / AW.
+// sbr_interest_econ.hip holds a copy of this function in two parts — interest_value_stage (down to
+// τ̄_IN, τ̄_OUT) and the κ loop of interest_econ_lane (the preamble and the three ways out below) —
+// because a shared stage changes equilibrium_kernel's machine code.  Edit one, edit the other.
 template <class P>
 __device__ __forceinline__ void solve_interest_point(P T, P G, P H, const Summ& S, const int n, const int ntau,
                                                      const int nle, const double ETA, const double T1,

@@ -43,7 +43,7 @@ struct InputArray {
 inline InputArray cols(const double* host, size_t w = 1) { return {host, w, true}; }
 inline InputArray shared(const double* host, size_t len) { return {host, len, false}; }
 
-constexpr int kMaxInputs = 8;
+constexpr int kMaxInputs = 10;
 using DevInputs = std::array<const double*, kMaxInputs>; // device pointer of each entry
 
 struct Inputs {

@@ -125,6 +125,16 @@ struct EconArgs {
     uint32_t* status;
 };
 
+// The rate axis of sbr_sweep_interest_econ (sbr_interest_econ.hip): n_rate pairs (r[d], delta[d]) in
+// HBM beside the axes of EconArgs, and the value function's integrator options.
+struct InterestEconArgs {
+    const double *r, *delta;
+    int32_t n_rate;
+    double rtol, atol;   // value-function Tsit5 tolerances, as InterestArgs
+    int64_t maxiters;
+    int64_t* steps;      // [n_beta][n_p][n_lam][n_rate][n_u] value-function RK steps (may be null)
+};
+
 // Hetero learning output: t [n_col][cap], G [n_col][cap][K], hr/hrI [n_col][K][cap].
 struct HeteroBufs {
     double* t;
@@ -290,6 +300,15 @@ hipError_t launch_hazard_econ(const double* beta, const double* eta, const Learn
                               const EconArgs& e, hipStream_t s);
 hipError_t launch_equilibrium_econ(const LearnBufs& L, const double* eta, const double* t_end, const double* u,
                                    const EqArgs& a, const EconArgs& e, const ResultSoA& out, hipStream_t s);
+// sbr_sweep_interest_econ, one chunk of classes, after launch_hazard_econ on the same e: the
+// rate × u plane of every (column, class) — lane j is (r, delta)[j / n_u] with u[j % n_u] — in tiles of
+// 512 lanes.  A lane integrates its value function once and then solves every kappa[c] on its
+// buffers: results at ((((column·n_p·n_lam + class)·n_rate + d)·n_kappa + c)·n_u + j % n_u), steps at
+// (((column·n_p·n_lam + class)·n_rate + d)·n_u + j % n_u).  a.lds_cap counts three staged arrays (t, G,
+// HR) as launch_interest's; a.n_u, a.kappa are ignored.
+hipError_t launch_interest_econ(const LearnBufs& L, const double* eta, const double* t_end, const double* u,
+                                const EqArgs& a, const EconArgs& e, const InterestEconArgs& ie,
+                                const ResultSoA& out, hipStream_t s);
 // hazard_rate (solver.jl:153-185) of n_beta columns whose knots, n_knots, n_le (#knots <= η) and
 // status are in L (the hazard stage of launch_learn_logistic on its own)
 hipError_t launch_hazard(const double* beta, const double* eta, const LearnArgs& a, const LearnBufs& L, int n_beta,

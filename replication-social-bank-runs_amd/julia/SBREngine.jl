@@ -182,6 +182,48 @@ function sweep_econ(ctx::Context, β_vals, u_vals; p = 0.5, κ = 0.6, λ = 0.01,
 end
 
 """
+    sweep_interest_econ(ctx, β_vals, u_vals; r, δ, p, κ, λ, η, tspan_end, x0)
+
+The interest-rate extension in every economic parameter at once: the product β × p × λ × (r, δ) × κ × u
+with `solve_learning` once per β and one value function per (β, p, λ, rate, u) — κ enters only
+`compute_ξ` and the AW pass of `solve_equilibrium_interest` (interest_rate_solver.jl:51-150).  `r` and
+`δ` are vectors of one length (pair d is `(r[d], δ[d])`; scalars are one pair); `p`, `κ`, `λ` are
+vectors or scalars; `η`/`tspan_end` are per-β (scalars broadcast).  Returns `(max_AW, ξ, τ̄_IN, τ̄_OUT,
+tolerance, status)` as arrays indexed `[u, κ, rate, λ, p, β]` (Julia's column-major view of the
+library's u-fastest layout) — `[:, c, d, b, a, :]` is `solve_equilibrium_interest_grid` at `(p[a],
+κ[c], λ[b], r[d], δ[d])` — and `rk_steps` indexed `[u, rate, λ, p, β]`: it has no κ axis.
+"""
+function sweep_interest_econ(ctx::Context, β_vals, u_vals; r, δ, p = 0.5, κ = 0.6, λ = 0.01, η = 15.0,
+                             tspan_end = 30.0, x0 = 1e-4)
+    β = collect(Float64, β_vals); u = collect(Float64, u_vals)
+    axis(x) = x isa Number ? Float64[x] : collect(Float64, x)
+    pv = axis(p); κv = axis(κ); λv = axis(λ); rv = axis(r); δv = axis(δ)
+    length(rv) == length(δv) ||
+        throw(ArgumentError("sweep_interest_econ: r and δ are pairs, got $(length(rv)) and $(length(δv)) values"))
+    nb, nu, np, nk, nl, nr = length(β), length(u), length(pv), length(κv), length(λv), length(rv)
+    col(x) = x isa Number ? fill(Float64(x), nb) : collect(Float64, x)
+    ηv = col(η); tv = col(tspan_end)
+    (length(ηv) == nb && length(tv) == nb) ||
+        throw(ArgumentError("sweep_interest_econ: η and tspan_end need length(β) = $nb entries"))
+    xi = Array{Float64}(undef, nu, nk, nr, nl, np, nb); tin = similar(xi); tout = similar(xi)
+    aw = similar(xi); tol = similar(xi); st = Array{UInt32}(undef, nu, nk, nr, nl, np, nb)
+    steps = Array{Int64}(undef, nu, nr, nl, np, nb)
+    opts = Ref(Opts(; early_exit = 0))
+    GC.@preserve β u pv κv λv rv δv ηv tv xi tin tout aw tol st steps begin
+        soa = Ref(ResultSoA(pointer(xi), pointer(tin), pointer(tout), pointer(aw), pointer(tol), pointer(st),
+                            Ptr{Int32}(C_NULL)))
+        rc = ccall((:sbr_sweep_interest_econ, libsbr), Cint,
+                   (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Float64, Ptr{Float64}, Int64, Int64,
+                    Ptr{Float64}, Int64, Ptr{Float64}, Int64, Ptr{Float64}, Ptr{Float64}, Int64, Ptr{Float64}, Int64,
+                    Ref{Opts}, Ref{ResultSoA}, Ptr{Int64}),
+                   ctx.ptr, β, ηv, tv, x0, u, nb, nu, pv, np, λv, nl, rv, δv, nr, κv, nk, opts, soa, steps)
+        check(ctx, rc)
+    end
+    return (max_AW = aw, ξ = xi, τ_bar_IN_UNC = tin, τ_bar_OUT_UNC = tout, tolerance = tol, status = st,
+            rk_steps = steps)
+end
+
+"""
     learn(ctx, β, tspan_end, x0; cap = 1 << 16)
 
 `solve_SIhomogeneous` (learning.jl:41-54) on the GPU: the knot grid `t` and CDF values `G`

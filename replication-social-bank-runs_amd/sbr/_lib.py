@@ -147,6 +147,10 @@ _SIGS = {
     "sbr_sweep_interest": (ctypes.c_int, [_P, _P, _P, _P, _D, _P, _I64, _I64, _D, _D, _D, _D, _D, _P, _P, _P]),
     "sbr_sweep_interest_dev": (ctypes.c_int, [_P, _P, _P, _P, _P, _D, _P, _I64, _I64, _D, _D, _D, _D, _D, _P, _P,
                                               _P]),
+    "sbr_sweep_interest_econ": (ctypes.c_int, [_P, _P, _P, _P, _D, _P, _I64, _I64, _P, _I64, _P, _I64, _P, _P, _I64,
+                                               _P, _I64, _P, _P, _P]),
+    "sbr_sweep_interest_econ_dev": (ctypes.c_int, [_P, _P, _P, _P, _P, _D, _P, _I64, _I64, _P, _I64, _P, _I64, _P,
+                                                   _P, _I64, _P, _I64, _P, _P, _P]),
 }
 
 _lib: ctypes.CDLL | None = None

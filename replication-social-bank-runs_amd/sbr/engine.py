@@ -341,6 +341,74 @@ class Engine:
         it caps the hazard classes (p, λ) solved per chunk (sbr_set_econ_workspace)."""
         check(self._L.sbr_set_econ_workspace(self._ctx, int(nbytes)), self._ctx, "sbr_set_econ_workspace")
 
+    # ------------------------------------------------------------------ β × p × λ × (r, δ) × κ × u
+    def sweep_interest_econ(self, beta, eta, t_end, u, p, kappa, lam, r, delta, x0=1e-4, max_iters: int = 100,
+                            knot_capacity: int = 65536, exhaustive: bool = False, flags: int = 0,
+                            out: dict | None = None, ode_rtol: float | None = None, ode_atol: float | None = None,
+                            ode_maxiters: int | None = None) -> dict:
+        """The interest-rate extension over the product of the axes in one call, each β learned and
+        each value function integrated once (sbr_sweep_interest_econ).  Axes as in ``sweep_econ``;
+        ``r`` and ``delta`` are arrays of one length, pair d being (r[d], delta[d]) (scalars: one
+        pair).  Returns arrays shaped (n_beta, n_p, n_lam, n_rate, n_kappa, n_u), the line
+        [i, a, b, d, c, :] being row i of ``sweep_interest`` at (p[a], kappa[c], lam[b], r[d],
+        delta[d]), and ``rk_steps`` shaped (n_beta, n_p, n_lam, n_rate, n_u): the value function
+        does not depend on κ.  ``out``: the caller's result arrays as in ``sweep_baseline``, with
+        an optional int64 ``rk_steps``."""
+        ax = interest_econ_axes(beta, eta, t_end, u, p, kappa, lam, r, delta)
+        shape = tuple(ax[k].size for k in ("beta", "p", "lam", "r", "kappa", "u"))
+        sshape = (*shape[:4], shape[5])
+        n, ns = int(np.prod(shape)), int(np.prod(sshape))
+        if out is None:
+            out = {k: np.empty(n) for k in RESULT_FIELDS}
+            out["status"] = np.empty(n, np.uint32)
+            out["iters"] = np.empty(n, np.int32)
+            rk = np.empty(ns, np.int64)
+        else:
+            rk = out.get("rk_steps")
+            out = host_result_views(out, n)
+            if rk is not None:
+                if not isinstance(rk, np.ndarray) or rk.dtype != np.int64 or rk.size != ns or not rk.flags["C_CONTIGUOUS"]:
+                    raise ArgumentError(f"out['rk_steps'] must be a C-contiguous int64 array of {ns}")
+                rk = rk.reshape(-1)
+        soa = _lib.ResultSoA(*[_ptr(out[k]) for k in (*RESULT_FIELDS, "status", "iters")])
+        opts = _opts(ode_rtol, ode_atol, ode_maxiters, early_exit_nan_run=0, bisect_max_iters=max_iters,
+                     knot_capacity=knot_capacity, flags=flags | (_lib.SBR_FLAG_EXHAUSTIVE if exhaustive else 0))
+        rc = self._L.sbr_sweep_interest_econ(self._ctx, _ptr(ax["beta"]), _ptr(ax["eta"]), _ptr(ax["t_end"]),
+                                             float(x0), _ptr(ax["u"]), shape[0], shape[5], _ptr(ax["p"]), shape[1],
+                                             _ptr(ax["lam"]), shape[2], _ptr(ax["r"]), _ptr(ax["delta"]), shape[3],
+                                             _ptr(ax["kappa"]), shape[4], ctypes.byref(opts), ctypes.byref(soa),
+                                             _ptr(rk))
+        check(rc, self._ctx, "sbr_sweep_interest_econ")
+        res = {k: (v.reshape(shape) if v is not None else None) for k, v in out.items()}
+        res["rk_steps"] = rk.reshape(sshape) if rk is not None else None
+        return res
+
+    def sweep_interest_econ_dev(self, beta, eta, t_end, u, p, kappa, lam, r, delta, x0, out: dict,
+                                stream: int | None = None, max_iters: int = 100, knot_capacity: int = 65536,
+                                exhaustive: bool = False, flags: int = 0, ode_rtol: float | None = None,
+                                ode_atol: float | None = None, ode_maxiters: int | None = None):
+        """Device-pointer variant on torch tensors (float64 cuda; ``eta`` and ``t_end`` as long as
+        ``beta``, each axis a tensor of one element or more, ``r`` and ``delta`` of one length) —
+        enqueue only, no host sync.  ``out`` holds preallocated tensors as for
+        ``sweep_baseline_dev``, each with n_beta·n_p·n_lam·n_rate·n_kappa·n_u elements, and an
+        optional int64 ``rk_steps`` with n_beta·n_p·n_lam·n_rate·n_u.  A point whose own u, p, λ, κ
+        or rate pair breaks its rule ends as SBR_ARG_INVALID."""
+        nb, nu, n_p, nl, nk, nr = beta.numel(), u.numel(), p.numel(), lam.numel(), kappa.numel(), r.numel()
+        if delta.numel() != nr:
+            raise ArgumentError(f"r and delta are pairs: got {nr} and {delta.numel()} values")
+        ns = nb * n_p * nl * nr * nu
+        soa = _lib.ResultSoA(*_out_ptrs(out, (*RESULT_FIELDS, "status", "iters"), ns * nk,
+                                        required=(*RESULT_FIELDS, "status")))
+        (rk,) = _out_ptrs(out, ("rk_steps",), ns)
+        opts = _opts(ode_rtol, ode_atol, ode_maxiters, early_exit_nan_run=0, bisect_max_iters=max_iters,
+                     knot_capacity=knot_capacity, flags=(_lib.SBR_FLAG_EXHAUSTIVE if exhaustive else 0) | flags)
+        rc = self._L.sbr_sweep_interest_econ_dev(
+            self._ctx, stream, _dptr(beta, "beta", _F64), _dptr(eta, "eta", _F64, nb),
+            _dptr(t_end, "t_end", _F64, nb), x0, _dptr(u, "u", _F64), nb, nu, _dptr(p, "p", _F64), n_p,
+            _dptr(lam, "lam", _F64), nl, _dptr(r, "r", _F64), _dptr(delta, "delta", _F64), nr,
+            _dptr(kappa, "kappa", _F64), nk, ctypes.byref(opts), ctypes.byref(soa), rk)
+        check(rc, self._ctx, "sbr_sweep_interest_econ_dev")
+
     def learn_baseline(self, beta, eta, t_end, x0=1e-4, stop_after_eta=False, cap=65536, tol=None,
                        ode_maxiters: int | None = None):
         beta = np.ascontiguousarray(beta, np.float64)
@@ -610,11 +678,12 @@ class Engine:
 
     def sweep_interest(self, beta, eta, t_end, u, p, kappa, lam, r, delta, x0=1e-4, max_iters: int = 100,
                        knot_capacity: int = 65536, ode_rtol: float | None = None, ode_atol: float | None = None,
-                       ode_maxiters: int | None = None) -> dict:
+                       ode_maxiters: int | None = None, flags: int = 0) -> dict:
         """Interest-rate extension over β columns × u (interest_rate_solver.jl:51-150 +
         get_AW_functions_interest!): the value function on the HR grid and buffers from
         h − rV (r > 0), the baseline for r = 0.  Returns [n_beta, n_u] arrays incl.
-        rk_steps (value-function Tsit5 steps per point)."""
+        rk_steps (value-function Tsit5 steps per point).  ``flags``: sbr_opts.flags (the
+        SBR_FLAG_DIAG_* stops, SBR_FLAG_EXHAUSTIVE)."""
         beta = np.ascontiguousarray(np.atleast_1d(beta), np.float64)
         nb = len(beta)
         eta = np.ascontiguousarray(np.broadcast_to(eta, (nb,)), np.float64)
@@ -627,7 +696,7 @@ class Engine:
         out["rk_steps"] = np.empty(nb * nu, np.int64)
         soa = _lib.ResultSoA(*[_ptr(out[k]) for k in (*RESULT_FIELDS, "status", "iters")])
         opts = _opts(ode_rtol, ode_atol, ode_maxiters, early_exit_nan_run=0, bisect_max_iters=max_iters,
-                     knot_capacity=knot_capacity)
+                     knot_capacity=knot_capacity, flags=flags)
         rc = self._L.sbr_sweep_interest(self._ctx, _ptr(beta), _ptr(eta), _ptr(t_end), x0, _ptr(u), nb, nu, p, kappa,
                                         lam, r, delta, ctypes.byref(opts), ctypes.byref(soa), _ptr(out["rk_steps"]))
         check(rc, self._ctx, "sbr_sweep_interest")
@@ -895,6 +964,21 @@ def econ_axes(beta, eta, t_end, u, p, kappa, lam) -> dict:
             raise ArgumentError(f"{name}: a scalar or a one-dimensional array")
         ax[name] = a
     return {k: np.ascontiguousarray(v) for k, v in ax.items()}
+
+
+def interest_econ_axes(beta, eta, t_end, u, p, kappa, lam, r, delta) -> dict:
+    """The nine arrays ``Engine.sweep_interest_econ`` hands to sbr_sweep_interest_econ: those of
+    ``econ_axes`` and the rate axis, ``r`` and ``delta`` as one-dimensional arrays of one length
+    (pair d is (r[d], delta[d]); scalars are one pair).  Pure Python."""
+    ax = econ_axes(beta, eta, t_end, u, p, kappa, lam)
+    for name, v in (("r", r), ("delta", delta)):
+        a = np.atleast_1d(np.asarray(v, np.float64))
+        if a.ndim != 1:
+            raise ArgumentError(f"{name}: a scalar or a one-dimensional array")
+        ax[name] = np.ascontiguousarray(a)
+    if ax["r"].size != ax["delta"].size:
+        raise ArgumentError(f"r and delta are pairs: got {ax['r'].size} and {ax['delta'].size} values")
+    return ax
 
 
 _ECON_AXES = ("u", "p", "kappa", "lam")
