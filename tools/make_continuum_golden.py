@@ -1,0 +1,358 @@
+#!/usr/bin/env python3
+"""Write tests/golden/continuum.json: seeded parameter lists with the continuum model's expected
+values (tests/continuum.py), for tests/test_continuum.py (oracle) and tests/test_gpu_continuum.py.
+
+    python tools/make_continuum_golden.py            # rewrites the fixture (about a minute)
+    python tools/make_continuum_golden.py --check    # regenerates and compares with the committed file
+
+Needs numpy, scipy and mpmath.  The lists and their expected values are the model alone; the built
+oracle is run on them afterwards only to record its largest deviations (meta.oracle), which must
+stay within half of each tolerance.
+
+The box (the issue's, narrowed twice for a stated reason):
+  β log-uniform [1, 60] (asked: from 0.3; the reference's trapezoid / linear-interpolation error in
+  a time scales like 1e-5/β and passes half the tolerance below β ≈ 1), η [3, 30], t_end [η, 2η],
+  p [.05, .95], κ [.1, .95], λ log-uniform [.002, .5], u log-uniform [.005, 2], x0 log-uniform
+  [1e-6, 1e-2], and G(η) ≥ 0.1 (where learning has not started by η the reference's knots, spaced by
+  its absolute tolerance, are ten times coarser).
+A drawn point that fails the conditioning verdict is dropped (lists) or masked (grids: ok = false);
+at most 10 % of all drawn points may be, or the tool fails.
+"""
+from __future__ import annotations
+
+import argparse
+import contextlib
+import io
+import json
+import math
+import sys
+from pathlib import Path
+
+import numpy as np
+
+REPO = Path(__file__).resolve().parent.parent
+sys.path[:0] = [str(REPO / "tests"), str(REPO / "oracle")]
+import continuum as C  # noqa: E402
+import continuum_cases as CC  # noqa: E402
+
+OUT = REPO / "tests" / "golden" / "continuum.json"
+BOX = dict(beta=(1.0, 60.0), eta=(3.0, 30.0), t_end_over_eta=(1.0, 2.0), p=(0.05, 0.95), kappa=(0.1, 0.95),
+           lam=(0.002, 0.5), u=(0.005, 2.0), x0=(1e-6, 1e-2), G_eta_min=0.1)
+SEEDS = dict(points=101, false_eq=102, econ=103, interest_econ=104, hetero=105)
+N_POINTS, N_FALSE = 96, 3
+HETERO_K = (1, 2, 3, 5, 8, 12, 16)
+MP_DIGITS = 45
+FIELDS = ("tau_in", "tau_out", "xi", "aw_max")
+
+
+def logu(rng, lo, hi):
+    return float(math.exp(rng.uniform(math.log(lo), math.log(hi))))
+
+
+def draw_x0(rng):
+    return logu(rng, *BOX["x0"])
+
+
+def draw_column(rng, x0):
+    """(β, η, t_end) inside the box, G(η) ≥ G_eta_min."""
+    while True:
+        beta, eta = logu(rng, *BOX["beta"]), float(rng.uniform(*BOX["eta"]))
+        t_end = eta * float(rng.uniform(*BOX["t_end_over_eta"]))
+        if float(C.G_of(eta, beta, x0)) >= BOX["G_eta_min"]:
+            return beta, eta, t_end
+
+
+def strata(rng, lo, hi, n, log=False):
+    """An axis of n increasing values: one draw from each of n equal parts of [lo, hi]."""
+    if log:
+        return [math.exp(v) for v in strata(rng, math.log(lo), math.log(hi), n)]
+    w = (hi - lo) / n
+    return [float(rng.uniform(lo + k * w, lo + (k + 1) * w)) for k in range(n)]
+
+
+def draw_econ(rng, kappa=None):
+    return dict(u=logu(rng, *BOX["u"]), p=float(rng.uniform(*BOX["p"])),
+                kappa=float(rng.uniform(*(kappa or BOX["kappa"]))), lam=logu(rng, *BOX["lam"]))
+
+
+def jnum(x):
+    x = float(x)
+    return None if x != x else x
+
+
+class Tally:
+    def __init__(self):
+        self.drawn = self.dropped = 0
+        self.reasons = {}
+
+    def add(self, res):
+        self.drawn += 1
+        if not res["ok"]:
+            self.dropped += 1
+            key = res["reason"].split(" at ")[0].split(" moves")[0].rstrip(" .0123456789")
+            self.reasons[key] = self.reasons.get(key, 0) + 1
+        return res["ok"]
+
+
+def make_points(tally):
+    rng = np.random.default_rng(SEEDS["points"])
+    x0 = draw_x0(rng)
+    pts, exp = [], []
+    while len(pts) < N_POINTS - N_FALSE:
+        beta, eta, t_end = draw_column(rng, x0)
+        q = dict(beta=beta, eta=eta, t_end=t_end, **draw_econ(rng))
+        res = C.solve(**q, x0=x0)
+        if tally.add(res):
+            pts.append(q)
+            exp.append(res)
+    # false equilibria need G(τ̄_IN) > (1 − κ)/2: a search of its own at κ ≥ 0.8; only its well-conditioned
+    # false equilibria are kept, and the draws it throws away for their class are not conditioning drops
+    rng = np.random.default_rng(SEEDS["false_eq"])
+    searched = 0
+    while len(pts) < N_POINTS:
+        beta, eta, t_end = draw_column(rng, x0)
+        q = dict(beta=beta, eta=eta, t_end=t_end, **draw_econ(rng, kappa=(0.8, BOX["kappa"][1])))
+        searched += 1
+        res = C.solve(**q, x0=x0, with_verdict=False)
+        if res["cls"] != "false":
+            continue
+        res = C.solve(**q, x0=x0)
+        if tally.add(res):
+            pts.append(q)
+            exp.append(res)
+    out = dict(x0=x0, false_eq_search_draws=searched)
+    for k in ("beta", "eta", "t_end", "u", "p", "kappa", "lam"):
+        out[k] = [q[k] for q in pts]
+    out["cls"] = [e["cls"] for e in exp]
+    for k in FIELDS:
+        out[k] = [jnum(e[k]) for e in exp]
+    return out
+
+
+def make_grid(tally, seed, n_beta, n_p, n_lam, n_kappa, n_u, rates=None):
+    """A product grid in sbr_sweep_econ's layout (i, a, b, c, j) or, with rate pairs, in
+    sbr_sweep_interest_econ's (i, a, b, d, c, j); flat C-order lists."""
+    rng = np.random.default_rng(seed)
+    x0 = draw_x0(rng)
+    cols = [draw_column(rng, x0) for _ in range(n_beta)]
+    ax = dict(p=strata(rng, *BOX["p"], n_p), lam=strata(rng, *BOX["lam"], n_lam, log=True),
+              kappa=strata(rng, *BOX["kappa"], n_kappa), u=strata(rng, *BOX["u"], n_u, log=True))
+    out = dict(x0=x0, beta=[c[0] for c in cols], eta=[c[1] for c in cols], t_end=[c[2] for c in cols], **ax)
+    if rates is not None:
+        out["r"], out["delta"] = [r for r, _ in rates], [d for _, d in rates]
+    out["cls"], out["ok"] = [], []
+    for k in FIELDS:
+        out[k] = []
+    for beta, eta, t_end in cols:
+        for p in ax["p"]:
+            for lam in ax["lam"]:
+                for r, delta in (rates or [(0.0, 0.1)]):
+                    for kappa in ax["kappa"]:
+                        for u in ax["u"]:
+                            res = C.solve(beta, eta, t_end, u, p, kappa, lam, x0, r, delta)
+                            out["ok"].append(bool(tally.add(res)))
+                            out["cls"].append(res["cls"])
+                            for k in FIELDS:
+                                out[k].append(jnum(res[k]))
+    shape = [n_beta, n_p, n_lam] + ([len(rates)] if rates else []) + [n_kappa, n_u]
+    out["shape"] = shape
+    assert len(out["cls"]) == int(np.prod(shape))
+    return out
+
+
+def make_hetero(tally):
+    """Equal group rates: K groups with one β and random unequal shares collapse to the baseline
+    model (ω = G because the shares sum to 1), with AW_max over the learning grid up to t_end and
+    without + G(0)."""
+    rng = np.random.default_rng(SEEDS["hetero"])
+    cases = []
+    while len(cases) < 3 * len(HETERO_K):
+        K = HETERO_K[len(cases) % len(HETERO_K)]
+        x0 = draw_x0(rng)
+        beta, eta, t_end = draw_column(rng, x0)
+        d = rng.random(K) + 0.2
+        d /= d.sum()
+        d[-1] = 1.0 - d[:-1].sum()
+        q = dict(beta=beta, eta=eta, t_end=t_end, **draw_econ(rng))
+        res = C.solve(**q, x0=x0, hetero=True)
+        if tally.add(res):
+            cases.append(dict(K=K, dist=[float(v) for v in d], x0=x0, **q, cls=res["cls"],
+                              **{k: jnum(res[k]) for k in FIELDS}))
+    return cases
+
+
+# ------------------------------------------------------------------------------------------------
+# the same model at MP_DIGITS digits: quadrature for I, bracketed root finding for the crossings,
+# and the value function in closed form between its switch points
+def mp_point(q, x0, r=0.0, delta=0.1, hetero=False):
+    import mpmath as mp
+
+    mp.mp.dps = MP_DIGITS
+    M = mp.mpf
+    beta, eta, t_end, u, p, kappa, lam = (M(q[k]) for k in ("beta", "eta", "t_end", "u", "p", "kappa", "lam"))
+    x0m, rm, dm = M(x0), M(r), M(delta)
+    A = (1 - x0m) / x0m
+    G = lambda t: 1 / (1 + A * mp.exp(-beta * t))  # noqa: E731
+    g = lambda t: beta * G(t) * (1 - G(t))  # noqa: E731
+    eg = lambda t: mp.exp(lam * t) * g(t)  # noqa: E731
+    th = mp.log(A) / beta
+
+    def quad(fn, a, b):
+        if a == b:
+            return M(0)
+        cuts = sorted({a, b, *[c for c in (th - 10 / beta, th, th + 10 / beta) if a < c < b]})
+        return mp.quad(fn, cuts)
+
+    I_eta = quad(eg, M(0), eta)
+    D = lambda I: p * I + (1 - p) * I_eta  # noqa: E731
+    # the float64 model's sign scan only names the brackets; every value below is mpmath's own
+    hz = C.hazard(float(q["beta"]), float(q["eta"]), float(q["lam"]), float(x0))
+    f64 = C._f_of(hz, float(q["u"]), float(q["p"]), float(r), float(delta))
+    s = hz.scan
+    above = f64(s) > 0.0
+    flips = np.flatnonzero(above[:-1] != above[1:])
+    c = dm - rm
+    # state at the left end a of the current piece: I(a), V(a)
+    a, Ia, Va = M(0), M(0), (u + dm) / (rm + dm)
+    ups, downs = [], []
+
+    def f_at(t, a, Ia, Va, in_B):
+        """f = h − rV − u at t ≥ a, V continued from (a, Va) with the piece's own formula."""
+        It = Ia + quad(eg, a, t)
+        h = p * eg(t) / D(It)
+        if rm == 0:
+            return h - u, It, None
+        if in_B:  # u + rV − h > 0: (V·D·e^{cτ})' = (δ + u)·D·e^{cτ}; ∫ I e^{cs} by parts
+            J = (It * mp.exp(c * t) - Ia * mp.exp(c * a)) / c - quad(lambda x: eg(x) * mp.exp(c * x), a, t) / c
+            K = p * J + (1 - p) * I_eta * (mp.exp(c * t) - mp.exp(c * a)) / c
+            V = (Va * D(Ia) * mp.exp(c * a) + (dm + u) * K) / (D(It) * mp.exp(c * t))
+        else:  # (1 − V)' = −(h + δ)(1 − V), exp(∫h) = D
+            V = 1 - (1 - Va) * D(Ia) / D(It) * mp.exp(-dm * (t - a))
+        return h - rm * V - u, It, V
+
+    in_B = not bool(above[0])  # f ≤ 0 ⇔ u + rV − h ≥ 0
+    f0 = f_at(M(0), a, Ia, Va, in_B)[0]
+    assert (f0 > 0) == bool(above[0])
+    for i in flips:
+        lo, hi = M(float(s[i])), M(float(s[i + 1]))
+        root = mp.findroot(lambda t: f_at(t, a, Ia, Va, in_B)[0], (lo, hi), solver="illinois", tol=M(10) ** -50,
+                           maxsteps=300, verify=False)
+        _, Ir, Vr = f_at(root, a, Ia, Va, in_B)
+        (ups if in_B else downs).append(root)
+        a, Ia, Va, in_B = root, Ir, Vr, not in_B
+    nan = float("nan")
+    if not above.any():
+        # the class itself at high precision: f at the float64 scan's maximum and at its neighbours
+        i = int(np.argmax(f64(s)))
+        assert all(f_at(M(float(s[j])), M(0), M(0), (u + dm) / (rm + dm), True)[0] < 0
+                   for j in (max(i - 1, 0), i, min(i + 1, len(s) - 1)))
+        return dict(cls="below", tau_in=float(t_end), tau_out=float(t_end), xi=nan, aw_max=nan)
+    tin = ups[0] if ups else M(0)
+    tout = downs[-1] if downs else eta
+    out = dict(cls="norun", tau_in=float(tin), tau_out=float(tout), xi=nan, aw_max=nan)
+    y = kappa + G(tin)
+    if y >= 1:
+        return out
+    xi = mp.log(y * A / (1 - y)) / beta
+    if xi > tout:
+        return out
+    if g(xi) < g(tin):
+        out["cls"] = "false"
+        return out
+    d = xi - tin
+    ts = min(th + d / 2, t_end if hetero else eta)
+    aw = G(ts) - (G(ts - d) if ts >= d else 0)
+    out.update(cls="run", xi=float(xi), aw_max=float(aw if hetero else aw + x0m))
+    return out
+
+
+def mp_check(fix):
+    """One point per class from `points`, an r > 0 run of the interest grid and a hetero run against
+    mpmath: the largest differences in a time and in AW_max."""
+    P, IE, H = fix["points"], fix["interest_econ"], fix["hetero"]
+    todo = []
+    for cls in C.CLASSES:
+        i = P["cls"].index(cls)
+        todo.append((f"points[{i}] {cls}", {k: P[k][i] for k in ("beta", "eta", "t_end", "u", "p", "kappa", "lam")},
+                     P["x0"], 0.0, 0.1, False, {k: P[k][i] for k in ("cls", *FIELDS)}))
+    sh = IE["shape"]
+    idx = np.arange(int(np.prod(sh))).reshape(sh)
+    for want in ("run", "norun"):
+        cand = [n for n in idx[:, :, :, [d for d, r in enumerate(IE["r"]) if r > 0]].ravel()
+                if IE["cls"][n] == want and IE["ok"][n] and IE["tau_in"][n] > 0]
+        if cand:
+            i, a_, b_, d_, c_, j_ = np.unravel_index(cand[len(cand) // 2], sh)
+            q = dict(beta=IE["beta"][i], eta=IE["eta"][i], t_end=IE["t_end"][i], u=IE["u"][j_], p=IE["p"][a_],
+                     kappa=IE["kappa"][c_], lam=IE["lam"][b_])
+            n = cand[len(cand) // 2]
+            todo.append((f"interest_econ[{i},{a_},{b_},{d_},{c_},{j_}] {want}", q, IE["x0"], IE["r"][d_],
+                         IE["delta"][d_], False, {k: IE[k][n] for k in ("cls", *FIELDS)}))
+    h = next(c for c in H if c["cls"] == "run")
+    todo.append(("hetero run", h, h["x0"], 0.0, 0.1, True, h))
+    dt = da = 0.0
+    names = []
+    for name, q, x0, r, delta, het, want in todo:
+        m = mp_point(q, x0, r, delta, het)
+        assert m["cls"] == want["cls"], (name, m["cls"], want["cls"])
+        for k in FIELDS:
+            w = want[k]
+            if w is None:
+                assert m[k] != m[k], (name, k)
+                continue
+            if k == "aw_max":
+                da = max(da, abs(m[k] - w))
+            else:
+                dt = max(dt, abs(m[k] - w))
+        names.append(name)
+    assert dt <= C.TOL_TIME / 1000 and da <= C.TOL_AW / 1000, (dt, da)
+    return dict(digits=MP_DIGITS, points=names, max_time_diff=dt, max_aw_diff=da)
+
+
+def build() -> dict:
+    tally = Tally()
+    fix = dict(points=make_points(tally),
+               econ=make_grid(tally, SEEDS["econ"], 3, 2, 2, 3, 8),
+               interest_econ=make_grid(tally, SEEDS["interest_econ"], 2, 2, 1, 2, 6, rates=[(0.0, 0.1), (0.05, 0.1)]),
+               hetero=make_hetero(tally))
+    share = tally.dropped / tally.drawn
+    if share > 0.10:
+        raise SystemExit(f"{tally.dropped} of {tally.drawn} drawn points are ill-conditioned: more than 10 %")
+    classes = {}
+    for lst in (fix["points"]["cls"], [c for c, ok in zip(fix["econ"]["cls"], fix["econ"]["ok"]) if ok],
+                [c for c, ok in zip(fix["interest_econ"]["cls"], fix["interest_econ"]["ok"]) if ok],
+                [c["cls"] for c in fix["hetero"]]):
+        for c in lst:
+            classes[c] = classes.get(c, 0) + 1
+    assert all(classes.get(c, 0) >= (2 if c == "false" else 1) for c in C.CLASSES), classes
+    fix["meta"] = dict(tol_time=C.TOL_TIME, tol_aw=C.TOL_AW, box={k: list(v) if isinstance(v, tuple) else v
+                                                                  for k, v in BOX.items()},
+                       seeds=SEEDS, drawn=tally.drawn, dropped=tally.dropped, dropped_share=share,
+                       dropped_reasons=tally.reasons, classes=classes, mpmath=mp_check(fix))
+    import oracle as O
+
+    with contextlib.redirect_stdout(io.StringIO()):
+        worst = CC.oracle_maxima(O, CC.load(json.dumps(fix)))
+    for name, d in worst.items():
+        if d["time"] > C.TOL_TIME / 2 or d["aw"] > C.TOL_AW / 2:
+            raise SystemExit(f"the oracle leaves half the tolerance on {name}: {d}")
+    fix["meta"]["oracle"] = worst
+    return fix
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--check", action="store_true", help="regenerate and compare with the committed fixture")
+    a = ap.parse_args()
+    text = json.dumps(build(), indent=1) + "\n"
+    if a.check:
+        same = OUT.read_text() == text
+        print("identical" if same else "DIFFERENT")
+        raise SystemExit(0 if same else 1)
+    OUT.write_text(text)
+    m = json.loads(text)["meta"]
+    print(f"{OUT.relative_to(REPO)}: {len(text)} bytes; drawn {m['drawn']}, dropped {m['dropped']} "
+          f"({100 * m['dropped_share']:.1f} %: {m['dropped_reasons']}); classes {m['classes']}; mpmath {m['mpmath']}; oracle {m['oracle']}")
+
+
+if __name__ == "__main__":
+    main()
