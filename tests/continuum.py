@@ -20,6 +20,9 @@ the limit of an infinitely fine knot grid:
     heterogeneity with equal rates (heterogeneity_solver.jl:316-375): the same with min(…, t_end)
     and without + x0.
 
+Heterogeneity with unequal group rates has no closed form: ``solve_hetero`` (below) integrates the
+K-group learning ODE and finds ξ, the validity path and AW_max numerically.
+
 I and V come from scipy's DOP853 with dense output at rtol 1e-13, the crossings from brentq after a
 sign scan.  Each point also carries the conditioning verdict ``ok`` (see ``verdict``): a point is
 ill-conditioned if a relative ±1e-4 on u or κ changes its class, or a relative ±1e-7 on u moves a
@@ -34,7 +37,7 @@ import math
 
 import numpy as np
 from scipy.integrate import solve_ivp
-from scipy.optimize import brentq
+from scipy.optimize import brentq, minimize_scalar
 
 TOL_TIME = 2e-5  # ξ, τ̄_IN, τ̄_OUT: the project's knot-grid sensitivity (tests/test_oracle_golden.py)
 TOL_AW = 1e-5    # AW_max
@@ -243,3 +246,207 @@ def hetero_learning(betas, dist, t_end, x0, t_eval, method="DOP853", rtol=RTOL, 
                   t_eval=np.asarray(t_eval, float), **kw)
     assert s.success, s.message
     return s.y.T
+
+
+# ------------------------------------------------------------------------------------------------
+# heterogeneity with unequal group rates (heterogeneity_learning.jl, heterogeneity_solver.jl)
+HETERO_CLASSES = CLASSES + ("invalid",)
+
+
+class HeteroLearning:
+    """G_k and I_k(τ) = ∫₀^τ e^{λs} g_k of the K-group learning ODE in one DOP853 solve to t_end:
+
+        G_k' = g_k = (1 − G_k) β_k ω,  ω = Σ_j dist_j G_j,  G_k(0) = x0
+        h_k(τ) = p e^{λτ} g_k(τ) / (p I_k(τ) + (1 − p) I_k(η))     on [0, η]
+
+    The sign-scan grids are uniform plus the integrator's own steps, which cluster where any group
+    rises."""
+
+    def __init__(self, betas, dist, eta, t_end, lam, x0):
+        self.betas, self.dist = np.asarray(betas, float), np.asarray(dist, float)
+        self.K, self.eta, self.t_end, self.lam, self.x0 = len(self.betas), eta, t_end, lam, x0
+        K, b, d = self.K, self.betas, self.dist
+
+        def rhs(t, y):
+            g = (1.0 - y[:K]) * b * float(d @ y[:K])
+            return np.concatenate([g, math.exp(lam * t) * g])
+
+        atol = np.concatenate([np.full(K, 1e-18), 1e-16 * b * x0])
+        s = solve_ivp(rhs, (0.0, t_end), np.concatenate([np.full(K, x0), np.zeros(K)]), method="DOP853", rtol=RTOL,
+                      atol=atol, dense_output=True)
+        assert s.success, s.message
+        self.sol, self.steps = s.sol, s.t
+        self.I_eta = s.sol(eta)[K:]
+        self.scan = self.grid(eta, N_SCAN)
+
+    def grid(self, hi, n):
+        return np.unique(np.concatenate([np.linspace(0.0, hi, n), self.steps[self.steps <= hi]]))
+
+    def G(self, k, t):
+        return self.sol(t)[k]
+
+    def g(self, k, t):
+        Y = self.sol(t)[:self.K]
+        return (1.0 - Y[k]) * self.betas[k] * (self.dist @ Y)
+
+    def h(self, k, t, p):
+        Y = self.sol(t)
+        g = (1.0 - Y[k]) * self.betas[k] * (self.dist @ Y[:self.K])
+        return p * np.exp(self.lam * np.asarray(t, float)) * g / (p * Y[self.K + k] + (1.0 - p) * self.I_eta[k])
+
+    @functools.cached_property
+    def h_over_p_scan(self):
+        """[K, n]: e^{λτ} g_k and I_k on the scan grid, from which h_k follows for any p."""
+        Y = self.sol(self.scan)
+        g = (1.0 - Y[:self.K]) * self.betas[:, None] * (self.dist @ Y[:self.K])[None, :]
+        return np.exp(self.lam * self.scan)[None, :] * g, Y[self.K:]
+
+
+@functools.lru_cache(maxsize=64)
+def _hetero_learning(betas, dist, eta, t_end, lam, x0) -> HeteroLearning:
+    return HeteroLearning(betas, dist, eta, t_end, lam, x0)
+
+
+def _hetero_buffers(L: HeteroLearning, u, p):
+    """(τ̄_IN [K], τ̄_OUT [K], below [K]): each group's pair from the sign of h_k − u, as ``_buffers``;
+    a group that never exceeds u gets t_end twice (optimal_buffer's fallback)."""
+    s = L.scan
+    eg, I = L.h_over_p_scan
+    tin, tout, below = np.empty(L.K), np.empty(L.K), np.zeros(L.K, bool)
+    for k in range(L.K):
+        above = p * eg[k] / (p * I[k] + (1.0 - p) * L.I_eta[k]) - u > 0.0
+        if not above.any():
+            tin[k] = tout[k] = L.t_end
+            below[k] = True
+            continue
+        up = np.flatnonzero(~above[:-1] & above[1:])
+        dn = np.flatnonzero(above[:-1] & ~above[1:])
+        fs = lambda x, k=k: float(L.h(k, x, p)) - u  # noqa: E731
+        tin[k] = brentq(fs, s[up[0]], s[up[0] + 1], xtol=XTOL, rtol=8.9e-16) if len(up) else 0.0
+        tout[k] = brentq(fs, s[dn[-1]], s[dn[-1] + 1], xtol=XTOL, rtol=8.9e-16) if len(dn) else L.eta
+    return tin, tout, below
+
+
+def _hetero_finish(L: HeteroLearning, buf, kappa, with_aw=True):
+    """Class, ξ and AW_max from the groups' buffers.  Also the quantities the verdict needs: aw_cap =
+    AW(max τ̄_OUT), slope, and path_gap, the smallest |path − κ| over the validity path's interior
+    local extrema."""
+    tin, tout, below = buf
+    K, dist, nan = L.K, L.dist, float("nan")
+    out = dict(cls="norun", tau_in=tin, tau_out=tout, xi=nan, aw_max=nan)
+    if below.all():
+        out["cls"] = "below"
+        return out
+    if not (tin[~below] < tout[~below]).all():
+        out["cls"] = "unmodelled"  # an up-crossing after the last down-crossing: not in the model
+        return out
+    ks = np.arange(K)
+
+    def AW(x):  # Σ dist_k [G_k(min(ξ, τ̄_OUT_k)) − G_k(min(ξ, τ̄_IN_k))], nondecreasing
+        Y = L.sol(np.concatenate([np.minimum(x, tout), np.minimum(x, tin)]))[:K]
+        return float(dist @ (Y[ks, ks] - Y[ks, K + ks]))
+
+    hi = float(tout[~below].max())
+    out["aw_cap"] = AW(hi)
+    if out["aw_cap"] < kappa:
+        return out
+    xi = hi if out["aw_cap"] == kappa else brentq(lambda x: AW(x) - kappa, 0.0, hi, xtol=XTOL, rtol=8.9e-16)
+    out["xi_root"] = xi
+    Y = L.sol(np.concatenate([np.minimum(xi, tout), np.minimum(xi, tin)]))[:K]
+    gY = (1.0 - Y) * L.betas[:, None] * (dist @ Y)[None, :]
+    out["slope"] = float(dist @ (gY[ks, ks] - gY[ks, K + ks]))
+    if out["slope"] < 0.0:
+        out["cls"] = "false"
+        return out
+    # is_valid_equilibrium_hetero: the path on [0, ξ] must not go from above κ to not above κ
+    tg = L.grid(xi, N_SCAN)
+    path = np.zeros(len(tg))
+    for k in range(K):
+        path += dist[k] * (L.G(k, tg) - L.G(k, np.maximum(0.0, tg - max(0.0, xi - tin[k]))))
+    above = path > kappa
+    d = np.diff(path)
+    ext = 1 + np.flatnonzero(d[:-1] * d[1:] < 0.0)
+    out["path_gap"] = float(np.abs(path[ext] - kappa).min()) if len(ext) else float("inf")
+    if (above[:-1] & ~above[1:]).any():
+        out["cls"] = "invalid"
+        return out
+    out.update(cls="run", xi=xi)
+    if not with_aw:
+        return out
+    # get_AW_hetero: the maximum over [0, t_end] of the summed shifted curves, without + x0
+    tinc, toutc = np.minimum(tin, xi), np.minimum(tout, xi)
+
+    def total(t):
+        t = np.asarray(t, float)
+        a = np.zeros_like(t)
+        for k in range(K):
+            so, si = t - xi + toutc[k], t - xi + tinc[k]
+            if toutc[k] == tinc[k]:
+                continue
+            a += dist[k] * (np.where(so >= 0.0, L.G(k, np.maximum(so, 0.0)), 0.0)
+                            - np.where(si >= 0.0, L.G(k, np.maximum(si, 0.0)), 0.0))
+        return a
+
+    tg = L.grid(L.t_end, 4 * N_SCAN)
+    v = total(tg)
+    i = int(np.argmax(v))
+    m = minimize_scalar(lambda t: -float(total(np.array([t]))[0]), bounds=(tg[max(i - 1, 0)], tg[min(i + 1, len(tg) - 1)]),
+                        method="bounded", options=dict(xatol=1e-11))
+    out["aw_max"] = max(float(v[i]), -float(m.fun))
+    out["aw_argmax"] = float(tg[i]) if float(v[i]) >= -float(m.fun) else float(m.x)
+    return out
+
+
+def _hetero_core(L, u, p, kappa, buf=None, with_aw=False):
+    buf = _hetero_buffers(L, u, p) if buf is None else buf
+    res = _hetero_finish(L, buf, kappa, with_aw)
+    res["_buf"] = buf
+    return res
+
+
+def verdict_hetero(L, base, u, p, kappa):
+    """``verdict``'s rules per group, and three of heterogeneity's own: AW(max τ̄_OUT) within a
+    relative 1e-4 of κ (below that the reference's interval collapse and its iteration cap are not
+    separable from a root), a slope that a relative 1e-4 on κ moves across 0, and a validity path
+    whose interior extrema come within 1e-4·κ of κ."""
+    if base["cls"] == "unmodelled":
+        return False, "unmodelled"
+    if "aw_cap" in base and abs(base["aw_cap"] - kappa) <= 1e-4 * kappa:
+        return False, "AW(max tau_out) within 1e-4 of kappa"
+    if base.get("path_gap", float("inf")) <= 1e-4 * kappa:
+        return False, "path within 1e-4 kappa of kappa"
+    for s in (-1e-4, 1e-4):
+        q = _hetero_core(L, u, p, kappa * (1.0 + s), buf=base["_buf"])
+        if q["cls"] != base["cls"]:
+            return False, f"class changes at kappa*(1{s:+g})"
+        if "slope" in base and "slope" in q and (q["slope"] < 0.0) != (base["slope"] < 0.0):
+            return False, f"slope changes sign at kappa*(1{s:+g})"
+        if _hetero_core(L, u * (1.0 + s), p, kappa)["cls"] != base["cls"]:
+            return False, f"class changes at u*(1{s:+g})"
+    for s, lim in ((-1e-7, TOL_TIME / 4), (1e-7, TOL_TIME / 4), (-H_REL, TOL_TIME / 2), (H_REL, TOL_TIME / 2)):
+        q = _hetero_core(L, u * (1.0 + s), p, kappa)
+        if q["cls"] != base["cls"]:
+            if abs(s) == 1e-7:
+                return False, f"class changes at u*(1{s:+g})"
+            continue
+        for k in ("tau_in", "tau_out", "xi"):
+            move = float(np.max(np.abs(np.asarray(q[k]) - np.asarray(base[k]))))  # NaN: both NaN in one class
+            if move > lim:
+                return False, f"{k} moves {move:.2e} at u*(1{s:+g})"
+    return True, ""
+
+
+def solve_hetero(betas, dist, eta, t_end, u, p, kappa, lam, x0, with_verdict=True, internals=False) -> dict:
+    """One point of the K-group continuum model: cls in HETERO_CLASSES (or "unmodelled"), tau_in and
+    tau_out per group [K], xi, aw_max (NaN where the class has none) and, with ``with_verdict``,
+    ok / reason; with ``internals`` also below [K], aw_cap, slope, path_gap and aw_argmax where the
+    class has them."""
+    eta, t_end, u, p, kappa, lam, x0 = (float(v) for v in (eta, t_end, u, p, kappa, lam, x0))
+    L = _hetero_learning(tuple(float(b) for b in betas), tuple(float(d) for d in dist), eta, t_end, lam, x0)
+    res = _hetero_core(L, u, p, kappa, with_aw=True)
+    if with_verdict:
+        res["ok"], res["reason"] = verdict_hetero(L, res, u, p, kappa)
+    res["below"] = res.pop("_buf")[2]
+    for k in () if internals else ("below", "xi_root", "aw_cap", "slope", "path_gap", "aw_argmax"):
+        res.pop(k, None)
+    return res

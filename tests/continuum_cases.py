@@ -16,7 +16,8 @@ TIMES = (("xi", "xi"), ("tau_in", "tau_in_unc"), ("tau_out", "tau_out_unc"))
 # status bits that say how the ODE was integrated, not how the point ended (include/sbr_status.h)
 INFO_BITS = 0x0800  # SBR_STIFF_SWITCH
 RUN, BELOW, COLLAPSE, MAXITER, FALSE_EQ = 0x3, 0x6, 0x8, 0x10, 0x20
-STATUS_OF = {"run": (RUN,), "below": (BELOW,), "norun": (COLLAPSE, MAXITER), "false": (FALSE_EQ,)}
+STATUS_OF = {"run": (RUN,), "below": (BELOW,), "norun": (COLLAPSE, MAXITER), "false": (FALSE_EQ,),
+             "invalid": (0x40,)}  # SBR_HETERO_INVALID
 
 
 def _arr(v):
@@ -91,8 +92,11 @@ def hetero_got(res: dict, K: int) -> list:
     return out
 
 
-def hetero_want(case: dict) -> dict:
-    return {k: _arr([case[k]]) for k in ("tau_in", "tau_out", "xi", "aw_max")}
+def hetero_want(case: dict, k: int | None = None) -> dict:
+    """The expected values of a hetero case for one group: the shared pair of an equal-rate case, or
+    group k's own pair of an unequal-rate one."""
+    pick = (lambda v: v) if k is None else (lambda v: v[k] if isinstance(v, list) else v)
+    return {f: _arr([pick(case[f])]) for f in ("tau_in", "tau_out", "xi", "aw_max")}
 
 
 # ---------------------------------------------------------------------------------------------
@@ -126,9 +130,22 @@ def oracle_grid(O, E: dict) -> dict:
     return out
 
 
+def hetero_betas(case: dict) -> np.ndarray:
+    return np.array([case["betas"]]) if "betas" in case else np.full((1, case["K"]), case["beta"])
+
+
 def oracle_hetero(O, case: dict) -> dict:
-    return O.sweep_hetero(np.full((1, case["K"]), case["beta"]), case["dist"], case["eta"], case["t_end"],
+    return O.sweep_hetero(hetero_betas(case), case["dist"], case["eta"], case["t_end"],
                           [case["u"]], case["p"], case["kappa"], case["lam"], case["x0"])
+
+
+def hetero_compare(res: dict, case: dict, what: str) -> dict:
+    """``compare`` on every group of a one-point result of an unequal-rate case; the largest deviations."""
+    worst = {"time": 0.0, "aw": 0.0}
+    for k, got in enumerate(hetero_got(res, case["K"])):
+        d = compare(got, [case["cls"]], hetero_want(case, k), [case["t_end"]], what=f"{what} K={case['K']} group {k}")
+        worst = {m: max(worst[m], d[m]) for m in worst}
+    return worst
 
 
 def oracle_maxima(O, fix: dict) -> dict:
@@ -144,4 +161,9 @@ def oracle_maxima(O, fix: dict) -> dict:
             d = compare(got, [case["cls"]], hetero_want(case), [case["t_end"]], what=f"oracle hetero {n} K={case['K']}")
             h = {k: max(h[k], d[k]) for k in h}
     out["hetero"] = h
+    h = {"time": 0.0, "aw": 0.0}
+    for n, case in enumerate(fix["hetero_unequal"]):
+        d = hetero_compare(oracle_hetero(O, case), case, f"oracle hetero_unequal {n}")
+        h = {k: max(h[k], d[k]) for k in h}
+    out["hetero_unequal"] = h
     return {k: {m: float(v) for m, v in d.items()} for k, d in out.items()}

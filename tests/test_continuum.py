@@ -80,6 +80,64 @@ def test_oracle_hetero_with_equal_rates(oracle, fix):
     assert past_eta >= 1
 
 
+def test_solve_hetero_with_equal_rates_is_solve(fix):
+    """The K-group model (DOP853 on (G_k, I_k), brentq for ξ, scans for the validity path and AW_max)
+    at equal rates against the closed-form model it must collapse to: every field to 1e-9."""
+    for case in fix["hetero"]:
+        a = C.solve(*[case[k] for k in CC.PARAMS], case["x0"], hetero=True)
+        b = C.solve_hetero([case["beta"]] * case["K"], case["dist"], case["eta"], case["t_end"], case["u"], case["p"],
+                           case["kappa"], case["lam"], case["x0"])
+        assert a["cls"] == b["cls"] == case["cls"] and b["ok"], (case["K"], a["cls"], b["cls"], b["reason"])
+        assert np.shape(b["tau_in"]) == np.shape(b["tau_out"]) == (case["K"],)
+        for k in VALUES:
+            if a[k] != a[k]:
+                assert np.isnan(b[k]).all(), k
+            else:
+                assert float(np.max(np.abs(np.asarray(b[k]) - a[k]))) <= 1e-9, (case["K"], k, b[k], a[k])
+
+
+def test_the_unequal_rate_list_is_what_the_issue_asks(fix):
+    H, m = fix["hetero_unequal"], fix["meta"]["hetero_unequal"]
+    assert len(H) == 48
+    assert {c["K"] for c in H} == {2, 3, 5, 8, 12, 16}
+    for c in H:
+        b, d = np.array(c["betas"]), np.array(c["dist"])
+        assert len(b) == len(d) == c["K"] and abs(d.sum() - 1.0) < 1e-15 and len(set(c["dist"])) == c["K"]
+        assert 1.5 * (1 - 1e-12) <= b.max() / b.min() <= 30.0 * (1 + 1e-12) and 1.0 <= b.min() and b.max() <= 60.0
+        rise = np.log((1 - c["x0"]) / c["x0"]) / float(d @ b)
+        assert 1.2 * rise <= c["eta"] * (1 + 1e-12) and c["eta"] <= 4.0 * rise * (1 + 1e-12)
+        assert 1.2 * c["eta"] * (1 - 1e-12) <= c["t_end"] <= 2.0 * c["eta"] * (1 + 1e-8)
+        assert 0 <= c["t_end_redraws"] <= 3
+        below = np.array(c["tau_in"]) == np.array(c["tau_out"])
+        assert c["mixed"] == bool(below.any() and not below.all())
+        assert (c["cls"] == "below") == bool(below.all())
+    assert all(c["betas"] != sorted(c["betas"]) for c in H if c["K"] > 3)  # shuffled: not in rate order
+    seen = [c["cls"] for c in H]
+    assert {k: seen.count(k) for k in set(seen)} == m["classes"]
+    assert sum(c["mixed"] for c in H) == m["mixed"] >= 6
+    assert seen.count("norun") >= 2 and seen.count("below") >= 2 and seen.count("false") >= 2
+    assert sum(c["t_end_redraws"] for c in H) == m["t_end_redraws"]
+    # drops, from conditioning and from the rounding BoundsError, within 10 % of all drawn points
+    M = fix["meta"]
+    assert m["dropped"] + M["dropped"] <= 0.10 * (m["drawn"] + M["drawn"])
+    assert m["dropped_share_all_lists"] == (m["dropped"] + M["dropped"]) / (m["drawn"] + M["drawn"])
+    mp = M["mpmath"]["hetero_unequal"]
+    assert mp["digits"] >= 30 and H[mp["case"]]["K"] == 2 and H[mp["case"]]["cls"] == "run"
+    assert mp["max_time_diff"] <= 1e-8 and mp["max_aw_diff"] <= 1e-9
+
+
+def test_oracle_hetero_with_unequal_rates(oracle, fix):
+    """Every group's own buffers, ξ, AW_max, the class and the sentinels of the oracle against the
+    K-group continuum model: what is specific to heterogeneity — the dist-weighted AW(ξ) with
+    per-group clipping, hazards from different pdf_k, groups below u beside groups with a window,
+    the maximum of a multi-humped AW_total."""
+    worst = {"time": 0.0, "aw": 0.0}
+    for n, case in enumerate(fix["hetero_unequal"]):
+        d = CC.hetero_compare(CC.oracle_hetero(oracle, case), case, f"oracle hetero_unequal {n}")
+        worst = {k: max(worst[k], d[k]) for k in worst}
+    _within_half(worst, fix["meta"]["oracle"]["hetero_unequal"])
+
+
 def test_the_fixture_is_reproducible(fix):
     """A seeded subset recomputed with tests/continuum.py: classes and verdicts equal, values to 1e-10."""
     rng = np.random.default_rng(5)
@@ -106,6 +164,13 @@ def test_the_fixture_is_reproducible(fix):
     for case in fix["hetero"][::5]:
         res = C.solve(*[case[k] for k in CC.PARAMS], case["x0"], hetero=True)
         same(res, case["cls"], {k: np.nan if case[k] is None else case[k] for k in VALUES}, True)
+    for case in fix["hetero_unequal"][::7]:
+        res = C.solve_hetero(case["betas"], case["dist"], *[case[k] for k in CC.PARAMS[1:]], case["x0"])
+        assert res["cls"] == case["cls"] and res["ok"]
+        for k in ("tau_in", "tau_out"):
+            assert float(np.max(np.abs(res[k] - np.array(case[k])))) <= 1e-10, k
+        for k in ("xi", "aw_max"):
+            assert (res[k] != res[k] and case[k] is None) or abs(res[k] - case[k]) <= 1e-10, k
 
 
 @pytest.mark.parametrize("K", [2, 3, 5, 8, 16])

@@ -74,3 +74,21 @@ def test_sweep_hetero_with_equal_rates(engine, fix, wide):
             worst = {k: max(worst[k], d[k]) for k in worst}
     print(f"gpu hetero wide={wide}: max |Δtime| {worst['time']:.3e}, max |ΔAW_max| {worst['aw']:.3e}")
     assert worst == fix["meta"]["oracle"]["hetero"]
+
+
+@pytest.mark.parametrize("wide", [False, True], ids=["specialised", "group-looped"])
+def test_sweep_hetero_with_unequal_rates(engine, fix, wide):
+    """Genuinely different group rates: every group's own buffers, ξ, AW_max, the class and the
+    sentinels against the K-group continuum model (tests/continuum.py, solve_hetero), one 1 × 1
+    sweep per case.  Without the flag K = 2, 3, 8 run the specialised kernels and 5, 12, 16 the
+    group-looped one."""
+    worst = {"time": 0.0, "aw": 0.0}
+    H = fix["hetero_unequal"]
+    assert {c["K"] for c in H} == {2, 3, 5, 8, 12, 16} and sum(c["mixed"] for c in H) >= 6
+    for n, case in enumerate(H):
+        r = engine.sweep_hetero(CC.hetero_betas(case), np.array(case["dist"]), case["eta"], case["t_end"], [case["u"]],
+                                case["p"], case["kappa"], case["lam"], x0=case["x0"], wide=wide)
+        d = CC.hetero_compare(r, case, f"gpu hetero_unequal {n}")
+        worst = {k: max(worst[k], d[k]) for k in worst}
+    print(f"gpu hetero_unequal wide={wide}: max |Δtime| {worst['time']:.3e}, max |ΔAW_max| {worst['aw']:.3e}")
+    assert worst == fix["meta"]["oracle"]["hetero_unequal"]

@@ -2,7 +2,7 @@
 """Write tests/golden/continuum.json: seeded parameter lists with the continuum model's expected
 values (tests/continuum.py), for tests/test_continuum.py (oracle) and tests/test_gpu_continuum.py.
 
-    python tools/make_continuum_golden.py            # rewrites the fixture (about a minute)
+    python tools/make_continuum_golden.py            # rewrites the fixture (about six minutes)
     python tools/make_continuum_golden.py --check    # regenerates and compares with the committed file
 
 Needs numpy, scipy and mpmath.  The lists and their expected values are the model alone; the built
@@ -15,6 +15,9 @@ The box (the issue's, narrowed twice for a stated reason):
   p [.05, .95], κ [.1, .95], λ log-uniform [.002, .5], u log-uniform [.005, 2], x0 log-uniform
   [1e-6, 1e-2], and G(η) ≥ 0.1 (where learning has not started by η the reference's knots, spaced by
   its absolute tolerance, are ten times coarser).
+The list hetero_unequal (C.solve_hetero, K groups at different rates) has ranges of its own (UNEQUAL)
+and one oracle-informed step, the t_end redraw on the reference's rounding BoundsError
+(make_hetero_unequal).
 A drawn point that fails the conditioning verdict is dropped (lists) or masked (grids: ok = false);
 at most 10 % of all drawn points may be, or the tool fails.
 """
@@ -39,8 +42,15 @@ OUT = REPO / "tests" / "golden" / "continuum.json"
 BOX = dict(beta=(1.0, 60.0), eta=(3.0, 30.0), t_end_over_eta=(1.0, 2.0), p=(0.05, 0.95), kappa=(0.1, 0.95),
            lam=(0.002, 0.5), u=(0.005, 2.0), x0=(1e-6, 1e-2), G_eta_min=0.1)
 SEEDS = dict(points=101, false_eq=102, econ=103, interest_econ=104, hetero=105)
+SEED_HETERO_UNEQUAL = 106
 N_POINTS, N_FALSE = 96, 3
 HETERO_K = (1, 2, 3, 5, 8, 12, 16)
+UNEQUAL_K = (2, 3, 5, 8, 12, 16)
+N_UNEQUAL, N_UNEQUAL_MIXED, N_UNEQUAL_FALSE = 48, 4, 2
+UNEQUAL = dict(mean_beta=(1.0, 20.0), spread=(1.5, 30.0), eta_over_rise=(1.2, 4.0), t_end_over_eta=(1.2, 2.0),
+               u_high=(0.1, 4.0), need=dict(mixed=6, norun=2, below=2, false=1))
+OOB_STATUS, MAX_REDRAWS, REDRAW = 0x80, 3, 1.0 + 2.0 ** -30
+MP_DIGITS_HETERO = 30
 MP_DIGITS = 45
 FIELDS = ("tau_in", "tau_out", "xi", "aw_max")
 
@@ -181,6 +191,169 @@ def make_hetero(tally):
     return cases
 
 
+def draw_unequal(rng, n, kappa=None, high_u=None):
+    """Case n's parameters: K cycles; rates log-uniform around a (geometric) mean with a spread ratio, shuffled;
+    unequal shares; η a multiple of the mean-rate logistic's rise time; every third case at high u."""
+    K = UNEQUAL_K[n % len(UNEQUAL_K)]
+    x0 = draw_x0(rng)
+    while True:  # every group's rate inside the box's β range, for the reason the box gives for its floor
+        mean, spread = logu(rng, *UNEQUAL["mean_beta"]), float(rng.uniform(*UNEQUAL["spread"]))
+        x = rng.uniform(-0.5, 0.5, K)
+        x[0], x[1] = -0.5, 0.5  # the slowest and the fastest group: max β / min β is the spread ratio itself
+        betas = mean * spread ** x
+        if BOX["beta"][0] <= betas.min() and betas.max() <= BOX["beta"][1]:
+            break
+    rng.shuffle(betas)
+    d = rng.random(K) + 0.2
+    d /= d.sum()
+    d[-1] = 1.0 - d[:-1].sum()
+    eta = float(rng.uniform(*UNEQUAL["eta_over_rise"])) * math.log((1.0 - x0) / x0) / float(d @ betas)
+    t_end = eta * float(rng.uniform(*UNEQUAL["t_end_over_eta"]))
+    econ = draw_econ(rng, kappa)
+    u_high = logu(rng, *UNEQUAL["u_high"])
+    if n % 3 == 2 if high_u is None else high_u:
+        econ["u"] = u_high
+    return dict(K=K, betas=[float(b) for b in betas], dist=[float(v) for v in d], x0=x0, eta=eta, t_end=t_end, **econ)
+
+
+def make_hetero_unequal(O):
+    """Unequal group rates (C.solve_hetero).  The model alone fixes each case and its verdict; the
+    oracle is then asked one thing: whether a predicted run ends in SBR_OOB, the reference's
+    BoundsError where (t_grid[end] − ξ) + ξ rounds one ulp above t_end.  Such a case is evaluated
+    again with t_end·(1 + 2⁻³⁰), at most three times, and dropped after that."""
+    rng = np.random.default_rng(SEED_HETERO_UNEQUAL)
+    tally = Tally()
+    cases, n_draw, oob_dropped, redraws, searched = [], 0, 0, 0, dict(mixed=0, false=0)
+    while len(cases) < N_UNEQUAL:
+        model = lambda q, **kw: C.solve_hetero(**{k: v for k, v in q.items() if k != "K"}, **kw)  # noqa: E731
+        if len(cases) < N_UNEQUAL - N_UNEQUAL_MIXED - N_UNEQUAL_FALSE:
+            q = draw_unequal(rng, n_draw)
+        elif len(cases) < N_UNEQUAL - N_UNEQUAL_FALSE:
+            # groups below u beside groups with a window, and false equilibria, are rare in the box: as for
+            # `points`, searches of their own, whose draws of another kind are not conditioning drops
+            q = draw_unequal(rng, n_draw, high_u=True)
+            searched["mixed"] += 1
+            below = model(q, with_verdict=False, internals=True)["below"]
+            if not below.any() or below.all():
+                n_draw += 1
+                continue
+        else:
+            q = draw_unequal(rng, n_draw, kappa=(0.8, BOX["kappa"][1]), high_u=False)
+            searched["false"] += 1
+            if model(q, with_verdict=False)["cls"] != "false":
+                n_draw += 1
+                continue
+        n_draw += 1
+        for redraw in range(MAX_REDRAWS + 1):
+            res = model(q, internals=True)
+            if not res["ok"] or res["cls"] != "run":
+                break
+            st = int(O.sweep_hetero(np.array([q["betas"]]), q["dist"], q["eta"], q["t_end"], [q["u"]], q["p"],
+                                    q["kappa"], q["lam"], q["x0"])["status"][0, 0]) & ~CC.INFO_BITS
+            if st != OOB_STATUS:
+                break
+            if redraw < MAX_REDRAWS:
+                q["t_end"] *= REDRAW
+        else:
+            res = dict(res, ok=False, reason="BoundsError after redraws")
+            oob_dropped += 1
+        if not tally.add(res):
+            continue
+        redraws += redraw
+        assert res["cls"] in C.HETERO_CLASSES
+        mixed = bool(res["below"].any() and not res["below"].all())
+        cases.append(dict(**q, cls=res["cls"], mixed=mixed, t_end_redraws=redraw,
+                          tau_in=[float(v) for v in res["tau_in"]], tau_out=[float(v) for v in res["tau_out"]],
+                          xi=jnum(res["xi"]), aw_max=jnum(res["aw_max"])))
+    classes = {}
+    for c in cases:
+        classes[c["cls"]] = classes.get(c["cls"], 0) + 1
+    n_mixed = sum(c["mixed"] for c in cases)
+    need = UNEQUAL["need"]
+    assert n_mixed >= need["mixed"] and all(classes.get(k, 0) >= need[k] for k in ("norun", "below", "false")), (
+        n_mixed, classes)
+    meta = dict(seed=SEED_HETERO_UNEQUAL, ranges={k: list(v) if isinstance(v, tuple) else v for k, v in UNEQUAL.items()},
+                drawn=tally.drawn, dropped=tally.dropped, dropped_reasons=tally.reasons, oob_dropped=oob_dropped,
+                search_draws=searched, t_end_redraws=redraws, classes=classes, mixed=n_mixed)
+    return cases, meta
+
+
+def mp_hetero(case):
+    """One K = 2 unequal-rate run with mpmath: Taylor integration (odefun) of (G_k, I_k) at
+    MP_DIGITS_HETERO digits; the crossings, ξ, the validity path and AW_max's hump are found by mpmath
+    scans of its own; returns the largest differences from the float64 model in a time and in AW_max."""
+    import mpmath as mp
+
+    mp.mp.dps = MP_DIGITS_HETERO
+    M = mp.mpf
+    K = case["K"]
+    b, d = [M(v) for v in case["betas"]], [M(v) for v in case["dist"]]
+    eta, t_end, u, p, kappa, lam, x0 = (M(case[k]) for k in ("eta", "t_end", "u", "p", "kappa", "lam", "x0"))
+
+    def F(t, y):
+        om = mp.fsum(d[j] * y[j] for j in range(K))
+        g = [(1 - y[k]) * b[k] * om for k in range(K)]
+        e = mp.exp(lam * t)
+        return g + [e * v for v in g]
+
+    sol = mp.odefun(F, 0, [x0] * K + [M(0)] * K)
+    sol(t_end)
+    I_eta = sol(eta)[K:]
+
+    def h(k, t):
+        y = sol(t)
+        return p * F(t, y)[K + k] / (p * y[K + k] + (1 - p) * I_eta[k])
+
+    # mpmath's own choices: a coarse scan of h_k − u names the first up-crossing and the last down-crossing,
+    # AW(ξ) = κ is bracketed by [0, max τ̄_OUT], and a coarse scan of AW_total names the hump; the float64
+    # model is only compared at the end
+    N = 400
+    root = lambda f, lo, hi: mp.findroot(f, (lo, hi), solver="illinois", tol=M(10) ** -50, maxsteps=300,  # noqa: E731
+                                         verify=False)
+    tin, tout = [], []
+    for k in range(K):
+        ts = [eta * j / N for j in range(N + 1)]
+        above = [h(k, t) - u > 0 for t in ts]
+        assert any(above)
+        ups = [j for j in range(N) if not above[j] and above[j + 1]]
+        dns = [j for j in range(N) if above[j] and not above[j + 1]]
+        tin.append(root(lambda t: h(k, t) - u, ts[ups[0]], ts[ups[0] + 1]) if ups else M(0))
+        tout.append(root(lambda t: h(k, t) - u, ts[dns[-1]], ts[dns[-1] + 1]) if dns else eta)
+
+    def AW(x):
+        return mp.fsum(d[k] * (sol(min(x, tout[k]))[k] - sol(min(x, tin[k]))[k]) for k in range(K))
+
+    assert AW(max(tout)) > kappa
+    xi = root(lambda x: AW(x) - kappa, M(0), max(tout))
+    slope = mp.fsum(d[k] * (F(min(xi, tout[k]), sol(min(xi, tout[k])))[k] - F(min(xi, tin[k]), sol(min(xi, tin[k])))[k])
+                    for k in range(K))
+    assert slope >= 0
+    tI = [max(0, xi - tin[k]) for k in range(K)]
+    path = [mp.fsum(d[k] * (sol(t)[k] - sol(max(0, t - tI[k]))[k]) for k in range(K)) for t in (xi * j / N for j in range(N))]
+    assert not any(path[j] > kappa and not path[j + 1] > kappa for j in range(N - 1))
+
+    def total(t):
+        a = M(0)
+        for k in range(K):
+            so, si = t - xi + min(tout[k], xi), t - xi + min(tin[k], xi)
+            a += d[k] * ((sol(max(so, 0))[k] if so >= 0 else 0) - (sol(max(si, 0))[k] if si >= 0 else 0))
+        return a
+
+    ts = [t_end * j / N for j in range(N + 1)]
+    v = [total(t) for t in ts]
+    j = max(range(N + 1), key=lambda q: v[q])
+    lo, hi = ts[max(j - 1, 0)], ts[min(j + 1, N)]
+    for _ in range(120):  # ternary search of the hump's cell pair: 1e-20 in t
+        a, b = lo + (hi - lo) / 3, hi - (hi - lo) / 3
+        lo, hi = (a, hi) if total(a) < total(b) else (lo, b)
+    aw = max(v[j], total((lo + hi) / 2))
+    want = C.solve_hetero(**{k: v for k, v in case.items() if k in ("betas", "dist", "eta", "t_end", "u", "p", "kappa",
+                                                                    "lam", "x0")}, with_verdict=False)
+    assert want["cls"] == "run"
+    dt = max(abs(float(a) - float(v)) for a, v in zip(tin + tout + [xi], [*want["tau_in"], *want["tau_out"], want["xi"]]))
+    return dt, abs(float(aw) - float(want["aw_max"]))
+
+
 # ------------------------------------------------------------------------------------------------
 # the same model at MP_DIGITS digits: quadrature for I, bracketed root finding for the crossings,
 # and the value function in closed form between its switch points
@@ -305,10 +478,19 @@ def mp_check(fix):
                 dt = max(dt, abs(m[k] - w))
         names.append(name)
     assert dt <= C.TOL_TIME / 1000 and da <= C.TOL_AW / 1000, (dt, da)
-    return dict(digits=MP_DIGITS, points=names, max_time_diff=dt, max_aw_diff=da)
+    out = dict(digits=MP_DIGITS, points=names, max_time_diff=dt, max_aw_diff=da)
+    # the first two-group run in which every buffer is a crossing, none a fallback (0, η or t_end)
+    n, h = next((n, c) for n, c in enumerate(fix["hetero_unequal"]) if c["K"] == 2 and c["cls"] == "run"
+                and min(c["tau_in"]) > 0.0 and max(c["tau_out"]) < c["eta"])
+    dt, da = mp_hetero(h)
+    assert dt <= 1e-8 and da <= 1e-9, (dt, da)
+    out["hetero_unequal"] = dict(digits=MP_DIGITS_HETERO, case=n, max_time_diff=dt, max_aw_diff=da)
+    return out
 
 
 def build() -> dict:
+    import oracle as O
+
     tally = Tally()
     fix = dict(points=make_points(tally),
                econ=make_grid(tally, SEEDS["econ"], 3, 2, 2, 3, 8),
@@ -324,12 +506,15 @@ def build() -> dict:
         for c in lst:
             classes[c] = classes.get(c, 0) + 1
     assert all(classes.get(c, 0) >= (2 if c == "false" else 1) for c in C.CLASSES), classes
+    fix["hetero_unequal"], unequal = make_hetero_unequal(O)
+    share_all = (tally.dropped + unequal["dropped"]) / (tally.drawn + unequal["drawn"])
+    if share_all > 0.10 or unequal["dropped"] > 0.10 * unequal["drawn"]:
+        raise SystemExit(f"{unequal['dropped']} of {unequal['drawn']} unequal-rate draws dropped; {share_all:.3f} of all")
+    unequal["dropped_share_all_lists"] = share_all
     fix["meta"] = dict(tol_time=C.TOL_TIME, tol_aw=C.TOL_AW, box={k: list(v) if isinstance(v, tuple) else v
                                                                   for k, v in BOX.items()},
                        seeds=SEEDS, drawn=tally.drawn, dropped=tally.dropped, dropped_share=share,
-                       dropped_reasons=tally.reasons, classes=classes, mpmath=mp_check(fix))
-    import oracle as O
-
+                       dropped_reasons=tally.reasons, classes=classes, hetero_unequal=unequal, mpmath=mp_check(fix))
     with contextlib.redirect_stdout(io.StringIO()):
         worst = CC.oracle_maxima(O, CC.load(json.dumps(fix)))
     for name, d in worst.items():
