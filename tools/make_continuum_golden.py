@@ -4,6 +4,10 @@ values (tests/continuum.py), for tests/test_continuum.py (oracle) and tests/test
 
     python tools/make_continuum_golden.py            # rewrites the fixture (about six minutes)
     python tools/make_continuum_golden.py --check    # regenerates and compares with the committed file
+    python tools/make_continuum_golden.py --social   # tests/golden/continuum_social.json: the social-learning fixed
+                                                     # point (tests/continuum_social.py), about ten minutes on 8 cores;
+                                                     # with --check it compares, with --margin it measures the stopping
+                                                     # margin again on 200 random points
 
 Needs numpy, scipy and mpmath.  The lists and their expected values are the model alone; the built
 oracle is run on them afterwards only to record its largest deviations (meta.oracle), which must
@@ -488,6 +492,278 @@ def mp_check(fix):
     return out
 
 
+# ------------------------------------------------------------------------------------------------
+# the social-learning fixed point (tests/continuum_social.py): tests/golden/continuum_social.json
+OUT_SOCIAL = REPO / "tests" / "golden" / "continuum_social.json"
+SOCIAL_BOX = dict(beta=(0.5, 20.0), x0=(1e-5, 1e-2), eta_over_rise=(1.2, 4.0), p=(0.05, 0.99), kappa=(0.1, 0.9),
+                  lam=(0.002, 0.5), u=(0.005, 2.0))
+SOCIAL_TOLS = (1e-3, 1e-4, 1e-5)
+SOCIAL_SEEDS = dict(groups=201, cap=202, past_eta=203, throws=204, below=205, false=206, margin=207)
+N_SOCIAL_GROUPS, SOCIAL_NB, SOCIAL_NU = 12, 2, 4
+SOCIAL_NEED = dict(throws=4, below=6, false=2)
+SOCIAL_FALSE_SEARCH = 400  # points searched for a false equilibrium of the returned iterate
+SOCIAL_SCRIPT = dict(p=0.99, kappa=0.25, lam=0.25, x0=1e-4, tol=1e-4, max_iter=500, beta=[0.9, 0.9], eta=[30 / 0.9] * 2,
+                     u=[0.5, 0.1, 0.3, 0.6])
+SOCIAL_SELF = 3  # points on which the tests repeat the model
+N_MARGIN = 200
+
+
+def draw_social_group(rng, n, max_iter=500, u_range=None, kappa=None):
+    x0 = logu(rng, *SOCIAL_BOX["x0"])
+    beta = [logu(rng, *SOCIAL_BOX["beta"]) for _ in range(SOCIAL_NB)]
+    eta = [float(rng.uniform(*SOCIAL_BOX["eta_over_rise"])) * math.log((1.0 - x0) / x0) / b for b in beta]
+    return dict(p=float(rng.uniform(*SOCIAL_BOX["p"])), kappa=float(rng.uniform(*(kappa or SOCIAL_BOX["kappa"]))),
+                lam=logu(rng, *SOCIAL_BOX["lam"]), x0=x0, tol=SOCIAL_TOLS[n % len(SOCIAL_TOLS)], max_iter=max_iter,
+                beta=beta, eta=eta, u=sorted(logu(rng, *(u_range or SOCIAL_BOX["u"])) for _ in range(SOCIAL_NU)))
+
+
+def social_points(grp):
+    return [dict(beta=grp["beta"][b], eta=grp["eta"][b], u=u, **{k: grp[k] for k in ("p", "kappa", "lam", "x0", "tol",
+                                                                                       "max_iter")})
+            for b in range(len(grp["beta"])) for u in grp["u"]]
+
+
+def social_model(q):
+    """The model alone on one point: its class (searches)."""
+    import continuum_social as CS
+
+    r = CS.solve_social(**q)
+    return r["cls"], r["fp_iters"]
+
+
+def social_oracle(q, stats=True):
+    import oracle as O
+    from sbr import julia_range
+
+    o = O.sweep_social([q["beta"]], q["eta"], [q["u"]], q["p"], q["kappa"], q["lam"], julia_range(0.0, q["eta"], 1000),
+                       x0=q["x0"], tol=q["tol"], max_iter=q["max_iter"], nthreads=1, stats=stats)
+    return {k: (int(v[0, 0]) if v.dtype.kind in "iu" else jnum(v[0, 0])) for k, v in o.items()}
+
+
+def social_knots(q):
+    """The oracle's learning knots of the returned iterate: rule (ii) takes the reference's knot spacing
+    at a jump from them."""
+    import oracle as O
+    from sbr import julia_range
+
+    return O.social_point(q["beta"], q["eta"], q["u"], q["p"], q["kappa"], q["lam"], julia_range(0.0, q["eta"], 1000),
+                          x0=q["x0"], tol=q["tol"], max_iter=q["max_iter"])["t"]
+
+
+def social_eval_group(pool, grp):
+    """Every point of a group; a column in which any point asks for the η redraw is evaluated again as a
+    whole at the new η (the sweep takes one η per β column), at most three times."""
+    grp = dict(grp, beta=list(grp["beta"]), eta=list(grp["eta"]), eta_redraws=[0] * len(grp["beta"]))
+    nu = len(grp["u"])
+    for _ in range(MAX_REDRAWS + 1):
+        pts = pool.map(social_eval_fixed, social_points(grp))
+        again = False
+        for b in range(len(grp["beta"])):
+            if any(pt["wants_redraw"] for pt in pts[b * nu:(b + 1) * nu]) and grp["eta_redraws"][b] < MAX_REDRAWS:
+                grp["eta"][b] *= REDRAW
+                grp["eta_redraws"][b] += 1
+                again = True
+        if not again:
+            break
+    for pt in pts:
+        if pt.pop("wants_redraw"):
+            pt.update(ok=False, reason="BoundsError after redraws")
+    grp["points"] = pts
+    return grp
+
+
+def social_eval_fixed(q):
+    """``social_eval`` without the redraw loop: wants_redraw says that the point asks for one."""
+    import continuum_social as CS
+
+    res = CS.solve_social(**q)
+    o = social_oracle(q)
+    ok, reason = CS.verdict_social(res, q["eta"], q["kappa"], q["tol"], social_knots(q))
+    oob = (o["status"] & (CS.OOB | CS.NOTCONV | 0x1)) == (CS.OOB | CS.NOTCONV)
+    wants = bool(ok and oob and (res["cls"] != "throws" or o["fp_iters"] < res["fp_iters"]))
+    margins = [abs(e - q["tol"]) / q["tol"] for e in res["errs"]]
+    return dict(cls=res["cls"], inner=res["inner"], fp_iters=res["fp_iters"], tau_in=jnum(res["tau_in"]),
+                tau_out=jnum(res["tau_out"]), xi=jnum(res["xi"]), aw_max=jnum(res["aw_max"]), ok=bool(ok), reason=reason,
+                wants_redraw=wants, min_margin=min(margins) if margins else None, n_knots=o["n_knots"],
+                oracle={k: o[k] for k in ("xi", "tau_in_unc", "tau_out_unc", "aw_max", "tol", "status", "iters",
+                                          "fp_iters")})
+
+
+def social_halved(q):
+    """(a): the model at CELLS and at 2·CELLS cells on one point: the largest change of a time and of AW_max
+    (None where the class or the iterate count changes)."""
+    import continuum_social as CS
+
+    a, b = CS.solve_social(**q), CS.solve_social(**q, cells=2 * CS.CELLS)
+    if (a["cls"], a["fp_iters"]) != (b["cls"], b["fp_iters"]):
+        return None
+    if a["cls"] == "throws":
+        return 0.0, 0.0
+    dt = max([abs(a[k] - b[k]) for k in ("tau_in", "tau_out", "xi") if a[k] == a[k]] or [0.0])
+    return dt, abs(a["aw_max"] - b["aw_max"]) if a["aw_max"] == a["aw_max"] else 0.0
+
+
+def social_closed_form(q):
+    """(b): G_n of the first three iterates from the closed form against DOP853 at rtol 1e-13 on
+    dG/dt = (1 − G) β AW_{n−1}(t), with the model's own AW_{n−1}: the largest difference on the grid."""
+    import continuum_social as CS
+    from scipy.integrate import solve_ivp
+
+    worst = [0.0]
+
+    def hook(n, t, A, G):
+        if n > 3:
+            return
+        te = t[::len(t) // 2000]
+        sol = solve_ivp(lambda x, y: (1.0 - y) * q["beta"] * np.interp(x, t, A), (0.0, float(t[-1])), [q["x0"]],
+                        method="DOP853", rtol=1e-13, atol=1e-16, t_eval=te, max_step=float(t[-1]) / 2000)
+        assert sol.success, sol.message
+        worst[0] = max(worst[0], float(np.abs(sol.y[0] - G[::len(t) // 2000][:len(te)]).max()))
+
+    CS.solve_social(**dict(q, max_iter=min(q["max_iter"], 3)), hook=hook)
+    return worst[0]
+
+
+def social_residual(q):
+    """The forced ODE's closed form on the oracle's own knots of the returned iterate."""
+    import continuum_social as CS
+    import oracle as O
+    from sbr import julia_range
+
+    r = O.social_point(q["beta"], q["eta"], q["u"], q["p"], q["kappa"], q["lam"], julia_range(0.0, q["eta"], 1000),
+                       x0=q["x0"], tol=q["tol"], max_iter=q["max_iter"])
+    return CS.forced_ode_residual(r["t"], r["G"], r["aw_old"], q["beta"], q["x0"])
+
+
+def make_social(margin=False) -> dict:
+    """tests/golden/continuum_social.json: a list of groups, each one sweep_social call of 2 β columns
+    (with their own η) × 4 u at one (p, κ, λ, x0, tol, max_iter)."""
+    import multiprocessing as mp
+
+    import continuum_social as CS
+
+    with mp.Pool(8) as pool:
+        groups, searched = [], {}
+
+        def add(grp, kind):
+            g = social_eval_group(pool, grp)
+            g["kind"] = kind
+            groups.append(g)
+            print(f"group {len(groups) - 1} {kind}: " + " ".join(f"{pt['cls']}/{pt['fp_iters']}{'' if pt['ok'] else '!'}"
+                                                                 for pt in g["points"]), file=sys.stderr)
+            return g
+
+        def count(cls):
+            return sum(pt["ok"] and pt["cls"] == cls and (cls != "past_eta" or pt["fp_iters"] == 501)
+                       for g in groups for pt in g["points"])
+
+        def search(name, want, need, limit, fp_iters=None, **kw):
+            """Groups from a seeded search of its own until ``need`` well-conditioned points of class ``want``
+            stand in the fixture; a drawn group without a candidate is of another kind, not a drop."""
+            rng = np.random.default_rng(SOCIAL_SEEDS[name])
+            n = searched.setdefault(name, 0)
+            while count(want) < need and n < limit:
+                grp = draw_social_group(rng, n, **kw)
+                n += 1
+                if any(c == want and (fp_iters is None or f == fp_iters)
+                       for c, f in pool.map(social_model, social_points(grp))):
+                    add(grp, name)
+            searched[name] = n
+
+        add(SOCIAL_SCRIPT, "script")
+        rng = np.random.default_rng(SOCIAL_SEEDS["groups"])
+        for n in range(N_SOCIAL_GROUPS):
+            add(draw_social_group(rng, n), "seeded")
+        rng = np.random.default_rng(SOCIAL_SEEDS["cap"])
+        add(draw_social_group(rng, 2, max_iter=7), "cap")
+        search("past_eta", "past_eta", 1, 40, fp_iters=501, max_iter=600, kappa=(0.6, 0.9), u_range=(0.1, 2.0))
+        search("throws", "throws", SOCIAL_NEED["throws"], 40)
+        search("below", "below", SOCIAL_NEED["below"], 40, u_range=(0.5, 2.0))
+        # a false equilibrium of the returned iterate needs g(ξ) < g(τ̄_IN): as in `points`, a search at κ ≥ 0.8
+        rng = np.random.default_rng(SOCIAL_SEEDS["false"])
+        n_false, false_groups = 0, []
+        while n_false < SOCIAL_FALSE_SEARCH and count("false") < SOCIAL_NEED["false"]:
+            grp = draw_social_group(rng, n_false // 8, kappa=(0.8, SOCIAL_BOX["kappa"][1]))
+            n_false += 8
+            if any(c == "false" for c, _ in pool.map(social_model, social_points(grp))):
+                add(grp, "false")
+        searched["false_points"] = n_false
+
+        pts = [(g, i, pt) for g in groups for i, pt in enumerate(g["points"])]
+        drawn, dropped, reasons, classes = len(pts), 0, {}, {}
+        for g, i, pt in pts:
+            if pt["ok"]:
+                classes[pt["cls"]] = classes.get(pt["cls"], 0) + 1
+                continue
+            dropped += 1
+            key = pt["reason"].split(" at ")[0].split(" moves")[0]
+            reasons[key] = reasons.get(key, 0) + 1
+        if dropped > 0.10 * drawn:
+            raise SystemExit(f"social: {dropped} of {drawn} drawn points dropped ({reasons}): more than 10 %")
+        assert classes.get("cap", 0) >= 1 and classes.get("past_eta", 0) >= 1, classes
+        assert all(classes.get(k, 0) >= v for k, v in SOCIAL_NEED.items() if k != "false"), classes
+        assert any(pt["cls"] == "past_eta" and pt["fp_iters"] == 501 and pt["ok"] for _, _, pt in pts)
+
+        # the oracle against the model, as the tests compare them
+        import oracle as O
+        from sbr import julia_range
+
+        worst = {"time": 0.0, "aw": 0.0}
+        for n, g in enumerate(groups):
+            a, kw = CS.group_args(g)
+            cmp = np.stack([julia_range(0.0, float(e), 1000) for e in g["eta"]])
+            d = CS.compare(O.sweep_social(*a, cmp, **kw), g, f"oracle group {n}")
+            worst = {k: max(worst[k], d[k]) for k in worst}
+        # (a) the grid cell halved, on every ok point; (b) the closed form against DOP853 on three points
+        ok_q = [CS.point_of(g, i) for g, i, pt in pts if pt["ok"]]
+        halves = pool.map(social_halved, ok_q, chunksize=1)
+        changed = sum(h is None for h in halves)
+        half = dict(time=max(h[0] for h in halves if h), aw=max(h[1] for h in halves if h), class_or_iterate_changed=changed)
+        pick = {}
+        for gi, g in enumerate(groups):
+            for i, pt in enumerate(g["points"]):
+                if pt["ok"] and pt["cls"] in ("run", "below", "cap") and pt["cls"] not in pick and pt["fp_iters"] <= 60:
+                    pick[pt["cls"]] = (gi, i)
+        self_pts = [pick[k] for k in ("run", "below", "cap")]
+        self_q = [CS.point_of(groups[gi], i) for gi, i in self_pts]
+        closed = max(pool.map(social_closed_form, self_q))
+        resid = pool.map(social_residual, self_q)
+        assert half["time"] <= C.TOL_TIME / 100 and half["aw"] <= C.TOL_AW / 100 and closed <= C.TOL_AW / 100, (half, closed)
+        meta = dict(tol_time=CS.TOL_TIME, tol_aw=CS.TOL_AW, cells=CS.CELLS, stop_margin=CS.STOP_MARGIN,
+                    knot_factor=CS.KNOT_FACTOR, throw_margin=CS.THROW_MARGIN,
+                    box={k: list(v) for k, v in SOCIAL_BOX.items()}, tols=list(SOCIAL_TOLS), seeds=SOCIAL_SEEDS,
+                    drawn=drawn, dropped=dropped, dropped_share=dropped / drawn, dropped_reasons=reasons,
+                    eta_redraws=sum(sum(g["eta_redraws"]) for g in groups), classes=classes, searched=searched,
+                    false_statement=(None if classes.get("false", 0) >= SOCIAL_NEED["false"] else
+                                     f"a search of {n_false} points at kappa >= 0.8 found {classes.get('false', 0)} "
+                                     "well-conditioned false equilibria of the returned iterate"),
+                    oracle=worst, halved_cell=half, closed_form_vs_dop853=closed,
+                    max_beta_knot_spacing=max(g["beta"][i // len(g["u"])] * g["eta"][i // len(g["u"])] / pt["n_knots"]
+                                              for g, i, pt in pts),
+                    self_points=[list(v) for v in self_pts],
+                    path_points=[dict(group=gi, point=i, oracle_residual=r, bound=2.0 * r)
+                                 for (gi, i), r in zip(self_pts, resid)])
+        if margin:
+            meta["stop_margin_measurement"] = social_margin(pool)
+    return dict(meta=meta, groups=groups)
+
+
+def social_margin(pool):
+    """Rule (i)'s margin: on N_MARGIN random points of the box, the largest min_n |err_n − tol| / tol among the
+    points that no other rule drops and on which model and oracle differ in fp_iters (none of them a BoundsError)."""
+    rng = np.random.default_rng(SOCIAL_SEEDS["margin"])
+    qs, k = [], 0
+    while len(qs) < N_MARGIN:
+        pts = social_points(draw_social_group(rng, k))
+        k += 1
+        qs += [pts[0], pts[5]]
+    out = pool.map(social_eval_fixed, qs, chunksize=1)
+    differ = [r for r in out if r["oracle"]["fp_iters"] != r["fp_iters"] and not r["oracle"]["status"] & 0x80]
+    by_margin = [r["min_margin"] for r in differ if r["ok"] or "stopping margin" in r["reason"]]
+    return dict(points=N_MARGIN, fp_iters_differ=len(differ), explained_by_other_rules=len(differ) - len(by_margin),
+                smallest_agreeing_margin=max(by_margin, default=0.0))
+
+
 def build() -> dict:
     import oracle as O
 
@@ -527,7 +803,25 @@ def build() -> dict:
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--check", action="store_true", help="regenerate and compare with the committed fixture")
+    ap.add_argument("--social", action="store_true", help="the social fixed point's fixture (continuum_social.json)")
+    ap.add_argument("--margin", action="store_true", help="with --social: measure the stopping margin again (200 points)")
     a = ap.parse_args()
+    if a.social:
+        sys.path.insert(0, str(REPO / "replication-social-bank-runs_amd"))
+        fix = make_social(a.margin)
+        if not a.margin and OUT_SOCIAL.exists():  # the measurement is kept from the run that made it
+            old = json.loads(OUT_SOCIAL.read_text())["meta"].get("stop_margin_measurement")
+            if old:
+                fix["meta"]["stop_margin_measurement"] = old
+        text = json.dumps(fix, indent=1) + "\n"
+        if a.check:
+            same = OUT_SOCIAL.read_text() == text
+            print("identical" if same else "DIFFERENT")
+            raise SystemExit(0 if same else 1)
+        OUT_SOCIAL.write_text(text)
+        print(f"{OUT_SOCIAL.relative_to(REPO)}: {len(text)} bytes; " + json.dumps({k: v for k, v in fix["meta"].items()
+                                                                                  if k not in ("box", "seeds")}))
+        return
     text = json.dumps(build(), indent=1) + "\n"
     if a.check:
         same = OUT.read_text() == text
