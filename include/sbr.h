@@ -384,6 +384,54 @@ int sbr_sweep_hetero_dev(sbr_ctx* ctx, void* stream, int32_t K, const double* be
                          sbr_result_soa* out, double* tau_in, double* tau_out);
 
 /*
+ * The heterogeneity sweep over every economic parameter at once — K groups × p × λ × κ × u,
+ * learning each column once (scripts/2_heterogeneity.jl:59 learns once and builds an
+ * EconomicParameters per solve).  solve_SInetwork_hetero depends on (βs, dist, tspan, x0) only, the
+ * K hazard paths on (column, η, p, λ) — one set per column and class (a, b) — the per-group buffers
+ * on (hazard paths, u), and κ enters only compute_ξ_hetero, the validity check and the AW pass.
+ * Every out field has n_col·n_p·n_lambda·n_kappa·n_u entries (iters may be NULL), element
+ * (c, a, b, k, j) at ((((c·n_p + a)·n_lambda + b)·n_kappa + k)·n_u + j), sbr_sweep_econ's layout;
+ * tau_in / tau_out (may be NULL) hold [that index][K].  The line [c, a, b, k, :] is exactly row c of
+ * sbr_sweep_hetero(K, betas, dist, eta, t_end, x0, u, …, p[a], kappa[k], lambda[b], opts, …): ξ,
+ * AW_max, tol, status (learning bits included), iters and the per-group buffers, at any sbr_opts
+ * (tolerances, ode_maxiters, knot_capacity, hetero_max_iters, SBR_FLAG_EXHAUSTIVE,
+ * SBR_FLAG_HETERO_WIDE).  out->tau_in_unc / tau_out_unc are ignored; η is per column (the caller
+ * resolves η_bar / Σ dist·βs); there is no early-exit post-pass, as sbr_sweep_hetero has none.
+ * SBR_EARG as sbr_sweep_hetero (K outside 1 … SBR_HETERO_MAX_K, group parameters, x0, u), and for an
+ * axis element that breaks 0 <= p <= 1, 0 < κ < 1 or λ > 0 (a NaN breaks its rule), a non-positive
+ * axis length, a null array, SBR_FLAG_XI_GUESS.  Host pointers; synchronous; a failed call writes
+ * none of the caller's arrays.  On an n-device context the columns are dealt cyclically with their
+ * n_p·n_lambda·n_kappa·n_u points, over either transport.
+ * Workspace: the hetero learning rows (t, G[K], hr[K], hrI[K] and six counters per column:
+ * (1 + 3K) × knot_capacity × 8 + 24 bytes) and, per class in flight, K HR rows, K running-integral
+ * rows and three words per column (2 × K × knot_capacity × 8 + 12 bytes).  With budget B
+ * (sbr_set_econ_workspace), max(1, (B − learning) / (n_col × (2 × K × knot_capacity × 8 + 12)))
+ * classes run per chunk, the chunks in stream order through the same rows; an allocation that fails
+ * anyway halves the chunk.  The results do not depend on the chunking.
+ */
+int sbr_sweep_hetero_econ(sbr_ctx* ctx, int32_t K, const double* betas, const double* dist, const double* eta,
+                          const double* t_end, double x0, const double* u, int64_t n_col, int64_t n_u,
+                          const double* p, int64_t n_p, const double* lambda, int64_t n_lambda, const double* kappa,
+                          int64_t n_kappa, const sbr_opts* opts, sbr_result_soa* out, double* tau_in,
+                          double* tau_out);
+/* Same on device pointers (the eight arrays, every out field and tau_in / tau_out in HBM), enqueued
+ * on `stream`; no host synchronisation.  The axes cannot be read on the host: a point whose own u,
+ * p, κ or λ breaks its rule ends with status == SBR_ARG_INVALID, ξ = AW_max = NaN, tol = Inf,
+ * iters = 0 and NaN group buffers (as in sbr_solve_points), and no other point is touched.  Needs a
+ * single-device context. */
+int sbr_sweep_hetero_econ_dev(sbr_ctx* ctx, void* stream, int32_t K, const double* betas, const double* dist,
+                              const double* eta, const double* t_end, double x0, const double* u, int64_t n_col,
+                              int64_t n_u, const double* p, int64_t n_p, const double* lambda, int64_t n_lambda,
+                              const double* kappa, int64_t n_kappa, const sbr_opts* opts, sbr_result_soa* out,
+                              double* tau_in, double* tau_out);
+/* Knots of the LDS slab the equilibrium launches of sbr_sweep_hetero_econ[_dev] stage a column's knot
+ * times in: 0 = the built-in slab, otherwise that many knots (at most the built-in slab).  Columns
+ * with more knots than the slab run the global-memory launch.  The results are the same; the setter
+ * exists so that tests reach that launch (no learned column exceeds the built-in slab).  An n-device
+ * context sets every rank's.  No other entry point is affected. */
+int sbr_set_hetero_econ_slab(sbr_ctx* ctx, int32_t knots);
+
+/*
  * n_batch heterogeneity grids that share K, dist, n_col, n_u, u and the scalars, swept back
  * to back and pipelined like sbr_sweep_baseline_batch_dev: the learning of batch k+1
  * (solve_SInetwork_hetero, latency-bound: one lane per column) runs on a highest-priority

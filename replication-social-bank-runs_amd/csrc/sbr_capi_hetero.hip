@@ -1,6 +1,6 @@
 // sbr_capi_hetero.hip — the heterogeneity extension's entry points of the C API: its learning
-// workspaces, sbr_learn_hetero, the sweeps (single, pipelined batch, host-pointer) and the
-// one-point paths.
+// workspaces, sbr_learn_hetero, the sweeps (single, pipelined batch, host-pointer), the one-point
+// paths and the product with the economic parameters (sbr_sweep_hetero_econ).
 #include "sbr_hostio.h"
 
 using namespace sbr_capi;
@@ -14,10 +14,31 @@ static void free_hetero_bufs(sbr::HeteroBufs& H, size_t& col, size_t& cap, size_
     col = cap = K = 0;
 }
 
+static void free_hetero_econ(sbr_ctx* c)
+{
+    free_dev(c->he_hr, c->he_hrI, c->he_cnt);
+    c->he_rows = c->he_ld = 0;
+}
+
 void free_hetero(sbr_ctx* c)
 {
     free_hetero_bufs(c->H, c->hs_col, c->hs_cap, c->hs_K);
     free_hetero_bufs(c->H2, c->hs2_col, c->hs2_cap, c->hs2_K);
+    free_hetero_econ(c);
+}
+
+// sbr_sweep_hetero_econ's class rows: `rows` (classes per chunk × columns) of K hazard rows and K
+// running-integral rows (ld = K × the learning stride doubles each) and three words
+static int ensure_hetero_econ(sbr_ctx* c, size_t rows, size_t ld)
+{
+    if (rows <= c->he_rows && ld == c->he_ld) return SBR_OK;
+    free_hetero_econ(c);
+    const int rc = alloc_dev(c, {{c->he_hr, rows * ld * sizeof(double)}, {c->he_hrI, rows * ld * sizeof(double)},
+                                 {c->he_cnt, rows * 3 * sizeof(int32_t)}});
+    if (rc) return rc;
+    c->he_rows = rows;
+    c->he_ld = ld;
+    return SBR_OK;
 }
 
 static int ensure_hetero_bufs(sbr_ctx* c, sbr::HeteroBufs& H, size_t& hcol, size_t& hcap, size_t& hK, size_t n_col,
@@ -330,6 +351,201 @@ int sbr_sweep_hetero(sbr_ctx* c, int32_t K, const double* betas, const double* d
         HIP_TRY(c, hipStreamSynchronize(s), SBR_EDEVICE);
         return SBR_OK;
     });
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------
+// sbr_sweep_hetero_econ: K groups × p × λ × κ × u
+// ---------------------------------------------------------------------------
+namespace {
+
+// workspace bytes (sbr.h: sbr_sweep_hetero_econ): a column's learning rows, and what a (column,
+// class) pair counts for against the budget
+size_t hetero_learn_bytes(size_t cap, size_t K) { return (1 + 3 * K) * cap * sizeof(double) + 6 * sizeof(int32_t); }
+size_t hetero_class_bytes(size_t cap, size_t K) { return 2 * K * cap * sizeof(double) + 3 * sizeof(int32_t); }
+
+// All in stream order on s: the learning launch of sbr_sweep_hetero once (its streamed hazard rows
+// are not read), then per chunk of hazard classes (p[a], λ[b]) the hazard launch — one wave per
+// (column, class) — and the equilibrium launches over the κ × u planes.  A chunk's hazards start
+// after the previous chunk's equilibria (they share the class rows); no host synchronisation.
+// Timing records: kind 0 = the learning launch, kind 1 = the hazard and equilibrium launches.
+int run_hetero_econ(sbr_ctx* c, hipStream_t s, int32_t K, const double* betas, const double* dist, const double* eta,
+                    const double* t_end, double x0, const double* u, int64_t n_col, int64_t n_u, const double* p,
+                    int64_t n_p, const double* lambda, int64_t n_lambda, const double* kappa, int64_t n_kappa,
+                    const sbr_opts& o, const sbr::ResultSoA& out, double* tin, double* tout)
+{
+    const size_t cap = (size_t)o.knot_capacity;
+    const int64_t n_class = n_p * n_lambda, plane = n_kappa * n_u;
+    size_t freeb = 0, total = 0;
+    (void)hipMemGetInfo(&freeb, &total);
+    const size_t held = c->hs_col * hetero_learn_bytes(c->hs_cap, c->hs_K) + 2 * c->he_rows * c->he_ld * sizeof(double);
+    const double budget = c->ec_budget > 0 ? (double)c->ec_budget : 0.4 * (double)(freeb + held);
+    const double left = budget - (double)n_col * (double)hetero_learn_bytes(cap, (size_t)K);
+    int64_t per = left > 0.0
+                      ? (int64_t)std::min(left / ((double)n_col * (double)hetero_class_bytes(cap, (size_t)K)), 65535.0)
+                      : 1;
+    per = std::max<int64_t>(1, std::min<int64_t>(per, n_class));
+    // one equilibrium launch holds the chunk's (column, class) pairs × the plane's tiles
+    while (per > 1 && !sbr::hetero_econ_grid(n_col, per, plane, 64)) per = (per + 1) / 2;
+    if (!sbr::hetero_econ_grid(n_col, per, plane, 64)) return fail(c, SBR_EARG, "grid size");
+    int rc = ensure_hetero(c, (size_t)n_col, cap, (size_t)K);
+    if (rc) return rc;
+    const sbr::HeteroBufs& L = c->H;
+    const size_t ld = (size_t)K * (size_t)L.cap;
+    // a workspace that already holds enough rows of this stride is used as it is
+    for (;;) {
+        rc = ensure_hetero_econ(c, (size_t)(per * n_col), ld);
+        if (rc == SBR_OK) break;
+        free_hetero_econ(c);
+        if (per == 1) return rc;
+        (void)hipGetLastError(); // the failed hipMalloc's error must not surface at the next launch check
+        per = (per + 1) / 2;
+    }
+    // p and λ are per class: the learning launch's streamed hazard (any valid pair) is a by-product
+    sbr::LearnArgs la{x0, o.ode_reltol, o.ode_abstol, 0.5, 1.0, o.ode_maxiters, (int32_t)n_col, 0, 0};
+    const int slab = c->he_slab > 0 ? std::min<int>(c->he_slab, het_lds(c)) : het_lds(c);
+    sbr::HeteroEqArgs ea{0.0, 1e-12, (int32_t)plane, o.hetero_max_iters, slab, (o.flags & SBR_FLAG_EXHAUSTIVE) ? 1 : 0,
+                         (o.flags >> 8) & 7, nullptr};
+    hipEvent_t t0 = tstart(c, s);
+    HIP_TRY(c, sbr::launch_hetero(K, betas, dist, eta, t_end, u, la, ea, L, out, tin, tout, s, 0), SBR_EDEVICE);
+    tend(c, s, 0, t0);
+    t0 = tstart(c, s);
+    int launches = 0;
+    for (int64_t g0 = 0; g0 < n_class; g0 += per) {
+        const int64_t ng = std::min<int64_t>(per, n_class - g0);
+        const size_t rows = (size_t)(per * n_col);
+        const sbr::HeteroEconArgs e{p, lambda, kappa, (int32_t)n_p, (int32_t)n_lambda, (int32_t)n_kappa, (int32_t)n_u,
+                                    (int32_t)n_col, (int32_t)g0, (int32_t)ng, c->he_hr, c->he_hrI, c->he_cnt,
+                                    c->he_cnt + rows, (uint32_t*)(c->he_cnt + 2 * rows)};
+        HIP_TRY(c, sbr::launch_hazard_hetero_econ(K, betas, dist, eta, L, e, s), SBR_EDEVICE);
+        HIP_TRY(c, sbr::launch_equilibrium_hetero_econ(K, dist, eta, t_end, u, ea, L, e, out, tin, tout, s,
+                                                       hetero_wide(o)), SBR_EDEVICE);
+        launches += 3;
+    }
+    tend(c, s, 1, t0, launches);
+    return SBR_OK;
+}
+
+// the checks sbr_sweep_hetero_econ and sbr_sweep_hetero_econ_dev share, before any array is looked at
+int hetero_econ_checks(sbr_ctx* c, const sbr_opts* opts, int32_t K, double x0, int64_t n_col, int64_t n_u, int64_t n_p,
+                       int64_t n_lambda, int64_t n_kappa)
+{
+    if (int rc = refuse_guess(c, opts)) return rc;
+    if (!c) return SBR_EARG;
+    if (!hetero_K_ok(K)) return fail(c, SBR_EARG, kHeteroKMsg);
+    const int64_t lim = 1 << 30;
+    if (n_col <= 0 || n_u <= 0 || n_p <= 0 || n_lambda <= 0 || n_kappa <= 0 || n_col > lim || n_u > lim ||
+        n_p > lim || n_lambda > lim || n_kappa > lim || n_p * n_lambda > lim || n_kappa * n_u > lim)
+        return fail(c, SBR_EARG, "grid size");
+    if (!(x0 >= 0.0)) return fail(c, SBR_EARG, "ArgumentError: Initial condition must be non-negative");
+    return SBR_OK;
+}
+
+// K groups × p × λ × κ × u on n devices: column i to rank i mod N with its n_p·n_lambda·n_kappa·n_u
+// points (and K buffers per point), the four axes to every rank
+int multi_sweep_hetero_econ(sbr_ctx* c, const Inputs& in, int32_t K, double x0, int64_t n_col, int64_t n_u,
+                            int64_t n_p, int64_t n_lambda, int64_t n_kappa, const sbr_opts& o, sbr_result_soa* out,
+                            double* tau_in, double* tau_out)
+{
+    const std::vector<FieldSpec> fs = {{out->xi, 8, 1},    {out->aw_max, 8, 1}, {out->tol, 8, 1},
+                                       {out->status, 4, 1}, {out->iters, 4, 1},  {tau_in, 8, (size_t)K},
+                                       {tau_out, 8, (size_t)K}};
+    auto run = [&](sbr_ctx* kid, hipStream_t s, int64_t nc, const DevInputs& d, const std::vector<void*>& f) -> int {
+        sbr_result_soa ro{(double*)f[0], nullptr, nullptr, (double*)f[1], (double*)f[2], (uint32_t*)f[3],
+                          (int32_t*)f[4]};
+        return sbr_sweep_hetero_econ_dev(kid, s, K, d[0], d[1], d[2], d[3], x0, d[4], nc, n_u, d[5], n_p, d[6],
+                                         n_lambda, d[7], n_kappa, &o, &ro, (double*)f[5], (double*)f[6]);
+    };
+    return fan_out(c, in, n_col, n_p * n_lambda * n_kappa * n_u, fs, o, run);
+}
+
+}  // namespace
+
+extern "C" {
+
+int sbr_sweep_hetero_econ_dev(sbr_ctx* c, void* stream, int32_t K, const double* betas, const double* dist,
+                              const double* eta, const double* t_end, double x0, const double* u, int64_t n_col,
+                              int64_t n_u, const double* p, int64_t n_p, const double* lambda, int64_t n_lambda,
+                              const double* kappa, int64_t n_kappa, const sbr_opts* opts, sbr_result_soa* out,
+                              double* tau_in, double* tau_out)
+{
+    int rc = hetero_econ_checks(c, opts, K, x0, n_col, n_u, n_p, n_lambda, n_kappa);
+    if (rc) return rc;
+    SBR_SINGLE_DEVICE(c);
+    if (!betas || !dist || !eta || !t_end || !u || !p || !lambda || !kappa || !out || !out->xi || !out->aw_max ||
+        !out->tol || !out->status)
+        return fail(c, SBR_EARG, "null array");
+    if (hipSetDevice(c->device) != hipSuccess) return fail(c, SBR_EDEVICE, "hipSetDevice");
+    const sbr_opts o = resolve(opts);
+    const sbr::ResultSoA r{out->xi, nullptr, nullptr, out->aw_max, out->tol, out->status, out->iters};
+    return fenced(c, stream, true, [&](hipStream_t s) {
+        return run_hetero_econ(c, s, K, betas, dist, eta, t_end, x0, u, n_col, n_u, p, n_p, lambda, n_lambda, kappa,
+                               n_kappa, o, r, tau_in, tau_out);
+    });
+}
+
+int sbr_sweep_hetero_econ(sbr_ctx* c, int32_t K, const double* betas, const double* dist, const double* eta,
+                          const double* t_end, double x0, const double* u, int64_t n_col, int64_t n_u,
+                          const double* p, int64_t n_p, const double* lambda, int64_t n_lambda, const double* kappa,
+                          int64_t n_kappa, const sbr_opts* opts, sbr_result_soa* out, double* tau_in, double* tau_out)
+{
+    int rc = hetero_econ_checks(c, opts, K, x0, n_col, n_u, n_p, n_lambda, n_kappa);
+    if (rc) return rc;
+    if (!betas || !dist || !eta || !t_end || !u || !p || !lambda || !kappa || !out) return fail(c, SBR_EARG, "null array");
+    rc = hetero_params_check(c, K, betas, dist, n_col);
+    if (!rc) rc = check_positive(c, n_col, {eta, t_end}, "ArgumentError: eta/t_end");
+    if (!rc) rc = check_u(c, u, n_u);
+    if (rc) return rc;
+    for (int64_t a = 0; a < n_p; a++)
+        if (!(p[a] >= 0.0 && p[a] <= 1.0)) return fail(c, SBR_EARG, "ArgumentError: p must be in [0, 1]");
+    rc = check_positive(c, n_lambda, {lambda}, "ArgumentError: lambda must be positive");
+    if (rc) return rc;
+    for (int64_t k = 0; k < n_kappa; k++)
+        if (!(kappa[k] > 0.0 && kappa[k] < 1.0)) return fail(c, SBR_EARG, "ArgumentError: kappa must be in (0, 1)");
+    const sbr_opts o = resolve(opts);
+    const Inputs in{cols(betas, (size_t)K),       shared(dist, (size_t)K), cols(eta),
+                    cols(t_end),                  shared(u, (size_t)n_u),  shared(p, (size_t)n_p),
+                    shared(lambda, (size_t)n_lambda), shared(kappa, (size_t)n_kappa)};
+    if (c->multi)
+        return multi_sweep_hetero_econ(c, in, K, x0, n_col, n_u, n_p, n_lambda, n_kappa, o, out, tau_in, tau_out);
+    if (hipSetDevice(c->device) != hipSuccess) return fail(c, SBR_EDEVICE, "hipSetDevice");
+    // the result block: xi, aw_max, tol | status, iters | tau_in, tau_out (K per point)
+    const size_t np = (size_t)n_col * (size_t)(n_p * n_lambda) * (size_t)(n_kappa * n_u);
+    void* dres;
+    rc = ensure_io(c, in, (size_t)n_col, np * (3 * 8 + 2 * 4 + 2 * (size_t)K * 8), &dres);
+    if (rc) return rc;
+    const auto d = in.dev(c->stage, (size_t)n_col);
+    double *dxi = (double*)dres, *daw = dxi + np, *dtol = daw + np;
+    uint32_t* dst = (uint32_t*)(dtol + np);
+    int32_t* dit = (int32_t*)(dst + np);
+    double* dtin = (double*)(dit + np);
+    double* dtout = dtin + np * K;
+    return fenced(c, nullptr, false, [&](hipStream_t s) -> int {
+        rc = in.stage(c, c->stage, (size_t)n_col, s);
+        if (rc) return rc;
+        const sbr::ResultSoA r{dxi, nullptr, nullptr, daw, dtol, dst, dit};
+        rc = run_hetero_econ(c, s, K, d[0], d[1], d[2], d[3], x0, d[4], n_col, n_u, d[5], n_p, d[6], n_lambda, d[7],
+                             n_kappa, o, r, tau_in ? dtin : nullptr, tau_out ? dtout : nullptr);
+        if (rc) return rc;
+        // the kernels finish before the first byte reaches the caller's arrays: a launch that failed
+        // on the device leaves them as they were
+        HIP_TRY(c, hipStreamSynchronize(s), SBR_EDEVICE);
+        rc = copy_out(c, s, {{out->xi, dxi, np * 8}, {out->aw_max, daw, np * 8}, {out->tol, dtol, np * 8},
+                             {out->status, dst, np * 4}, {out->iters, dit, np * 4},
+                             {tau_in, dtin, np * K * 8}, {tau_out, dtout, np * K * 8}});
+        if (rc) return rc;
+        HIP_TRY(c, hipStreamSynchronize(s), SBR_EDEVICE);
+        return SBR_OK;
+    });
+}
+
+int sbr_set_hetero_econ_slab(sbr_ctx* c, int32_t knots)
+{
+    if (!c || knots < 0) return SBR_EARG;
+    for (int r = 0; c->multi && r < sbr_multi_size(c); r++) sbr_multi_child(c, r)->he_slab = knots; // every rank's own
+    c->he_slab = knots;
+    return SBR_OK;
 }
 
 }  // extern "C"

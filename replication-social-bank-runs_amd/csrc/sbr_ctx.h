@@ -138,6 +138,13 @@ struct sbr_ctx {
     int32_t* ec_cnt = nullptr; // n_tau [ec_rows], n_le [ec_rows], status [ec_rows]
     size_t ec_rows = 0, ec_ld = 0;
     int64_t ec_budget = 0; // 0: 40 % of the free plus the already held HBM
+    // sbr_sweep_hetero_econ: the K HR rows and K running-integral rows, τ̄ counters and status words of
+    // the hazard classes in flight (he_rows rows of stride he_ld = K × the learning stride: classes
+    // per chunk × columns); its budget is ec_budget
+    double *he_hr = nullptr, *he_hrI = nullptr;
+    int32_t* he_cnt = nullptr; // n_tau [he_rows], n_le [he_rows], status [he_rows]
+    size_t he_rows = 0, he_ld = 0;
+    int32_t he_slab = 0; // sbr_set_hetero_econ_slab: knots of the equilibrium launches' LDS slab (0: het_lds())
     size_t ev_used = 0;
     struct TRec {
         int kind; // 0 learning (+ hazard), 1 equilibrium

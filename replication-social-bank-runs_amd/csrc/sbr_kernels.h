@@ -163,6 +163,22 @@ struct HeteroEqArgs {
     int32_t n_col;      // set by the launcher (XCD-aware 1-D grid)
 };
 
+// The heterogeneity line's economic-parameter sweep (sbr_hetero_econ.hip, sbr_hetero_econ_wide.hip):
+// the axes and one chunk of hazard classes, as EconArgs.  Row (k·n_col + column) belongs to class
+// class0 + k: K hazard rows and K running-integral rows of stride L.cap, and the class's own n_tau,
+// n_le and status word per column — the classes of a column never write the same word, and none
+// writes the learning kernel's.
+struct HeteroEconArgs {
+    const double *p, *lam, *kappa; // the axes, in HBM
+    int32_t n_p, n_lam, n_kappa, n_u, n_col;
+    int32_t class0, n_class;
+    double* hr;        // [n_class][n_col][K][L.cap]
+    double* hrI;       // [n_class][n_col][K][L.cap]
+    int32_t* n_tau;    // [n_class][n_col]
+    int32_t* n_le;
+    uint32_t* status;
+};
+
 // Promotion pool of the social sweep: a point whose iterate outgrows the knot
 // capacity moves (AW_{n-1} and its carried state) into a free slot here and
 // redoes that iterate from the pool blocks of the same or the next launch,
@@ -265,6 +281,27 @@ hipError_t launch_hetero_learn_wide(int K, const double* betas, const double* di
 hipError_t launch_hetero_aw_groups_wide(int K, const double* T, const double* G, const int32_t* n_dev, int n_max,
                                         const double* xi, const double* tin, const double* tout,
                                         const uint32_t* status, double* out, size_t ld, hipStream_t s);
+
+// sbr_sweep_hetero_econ, one chunk of classes, on the knots and group CDFs launch_hetero's phase 0
+// left in L.  launch_hazard_hetero_econ: one wave per (column, class of the chunk) runs
+// hazard_hetero_kernel's loop with the class's p, λ into the class's rows and words of e (la.p /
+// la.lam are ignored).  launch_equilibrium_hetero_econ: the κ × u plane of every (column, class) —
+// point j is (kappa[j / n_u], u[j % n_u]) — results at ((column·n_p·n_lam + class)·n_kappa·n_u + j),
+// buffers at that index · K; ea.n_u and ea.kappa are ignored.  K = 1, 2, 3, 4, 8 run the specialised
+// kernel, every other K and `wide` the group-looped one (launch_equilibrium_hetero_econ_wide).
+// The 1-D grid of one of its equilibrium launches (workgroups of bs lanes over planes of `plane`
+// points): tiles × the (column, class) pairs rounded up to the eight XCDs; 0 if that exceeds a launch.
+unsigned hetero_econ_grid(int64_t n_col, int64_t n_class, int64_t plane, int bs);
+hipError_t launch_hazard_hetero_econ(int K, const double* betas, const double* dist, const double* eta,
+                                     const HeteroBufs& L, const HeteroEconArgs& e, hipStream_t s);
+hipError_t launch_equilibrium_hetero_econ(int K, const double* dist, const double* eta, const double* t_end,
+                                          const double* u, const HeteroEqArgs& ea, const HeteroBufs& L,
+                                          const HeteroEconArgs& e, const ResultSoA& out, double* tin, double* tout,
+                                          hipStream_t s, bool wide);
+hipError_t launch_equilibrium_hetero_econ_wide(int K, const double* dist, const double* eta, const double* t_end,
+                                               const double* u, const HeteroEqArgs& ea, const HeteroBufs& L,
+                                               const HeteroEconArgs& e, const ResultSoA& out, double* tin,
+                                               double* tout, hipStream_t s);
 
 hipError_t launch_learn_logistic(const double* beta, const double* eta, const double* t_end, const LearnArgs& a,
                                  const LearnBufs& L, hipStream_t s);

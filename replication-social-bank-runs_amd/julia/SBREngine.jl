@@ -345,6 +345,42 @@ function solve_equilibrium_hetero_grid(ctx::Context, βs_cols::AbstractMatrix, d
 end
 
 """
+    sweep_hetero_econ(ctx, βs_cols, dist, u_vals; η, tspan_end, x0, p, κ, λ)
+
+The heterogeneity model in every economic parameter at once: the product column × p × λ × κ × u with
+`solve_SInetwork_hetero` once per column (scripts/2_heterogeneity.jl:59 learns once) and
+`solve_equilibrium_hetero(lr, EconomicParameters(u, p, κ, λ, η_bar, η))` per combination.  `βs_cols` is
+K × n_col, η per column; `p`, `κ`, `λ` are vectors or scalars (a scalar is an axis of length 1).
+Returns `(AW_max, ξ, tolerance, status)` indexed `[u, κ, λ, p, column]` (Julia's column-major view of
+the library's u-fastest layout) and the group buffers `τ_bar_IN_UNCs`, `τ_bar_OUT_UNCs` indexed
+`[group, u, κ, λ, p, column]`; `[:, k, b, a, :]` is `solve_equilibrium_hetero_grid` at
+`(p[a], κ[k], λ[b])`.
+"""
+function sweep_hetero_econ(ctx::Context, βs_cols::AbstractMatrix, dist, u_vals; η, tspan_end, x0 = 1e-4,
+                           p = 0.9, κ = 0.3, λ = 0.1)
+    B = Matrix{Float64}(βs_cols); K, nc = size(B)
+    d = collect(Float64, dist); u = collect(Float64, u_vals); nu = length(u)
+    axis(x) = x isa Number ? Float64[x] : collect(Float64, x)
+    pv = axis(p); κv = axis(κ); λv = axis(λ)
+    np, nk, nl = length(pv), length(κv), length(λv)
+    ηv = collect(Float64, η); tv = fill(Float64(tspan_end), nc) .+ 0 .* ηv
+    xi = Array{Float64}(undef, nu, nk, nl, np, nc); aw = similar(xi); tol = similar(xi)
+    st = Array{UInt32}(undef, nu, nk, nl, np, nc)
+    tin = Array{Float64}(undef, K, nu, nk, nl, np, nc); tout = similar(tin)
+    opts = Ref(Opts(; early_exit = 0))
+    GC.@preserve B d u pv κv λv ηv tv xi aw tol st tin tout begin
+        soa = Ref(ResultSoA(pointer(xi), C_NULL, C_NULL, pointer(aw), pointer(tol), pointer(st), C_NULL))
+        rc = ccall((:sbr_sweep_hetero_econ, libsbr), Cint,
+                   (Ptr{Cvoid}, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Float64,
+                    Ptr{Float64}, Int64, Int64, Ptr{Float64}, Int64, Ptr{Float64}, Int64, Ptr{Float64}, Int64,
+                    Ref{Opts}, Ref{ResultSoA}, Ptr{Float64}, Ptr{Float64}),
+                   ctx.ptr, K, B, d, ηv, tv, x0, u, nc, nu, pv, np, λv, nl, κv, nk, opts, soa, tin, tout)
+        check(ctx, rc)
+    end
+    return (AW_max = aw, ξ = xi, tolerance = tol, τ_bar_IN_UNCs = tin, τ_bar_OUT_UNCs = tout, status = st)
+end
+
+"""
     solve_equilibrium_social_learning_grid(ctx, β_vals, u_vals; η, x0, p, κ, λ, tol=1e-4, max_iter=500)
 
 Batched `solve_equilibrium_social_learning(ModelParameters(…); tol, max_iter)`

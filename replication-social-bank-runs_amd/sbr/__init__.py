@@ -16,6 +16,7 @@ from .engine import (  # noqa: F401
     econ_axes,
     econ_from_model,
     get_AW_functions,
+    hetero_econ_axes,
     interest_econ_axes,
     SolvedModelHetero,
     SolvedModelInterest,

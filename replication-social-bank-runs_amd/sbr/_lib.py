@@ -126,6 +126,11 @@ _SIGS = {
                                             _P]),
     "sbr_sweep_hetero_batch_dev": (ctypes.c_int, [_P, _P, _I64, _I32, _P, _P, _P, _P, _D, _P, _I64, _I64, _D, _D,
                                                   _D, _P, _P, _P, _P]),
+    "sbr_sweep_hetero_econ": (ctypes.c_int, [_P, _I32, _P, _P, _P, _P, _D, _P, _I64, _I64, _P, _I64, _P, _I64, _P,
+                                             _I64, _P, _P, _P, _P]),
+    "sbr_sweep_hetero_econ_dev": (ctypes.c_int, [_P, _P, _I32, _P, _P, _P, _P, _D, _P, _I64, _I64, _P, _I64, _P,
+                                                 _I64, _P, _I64, _P, _P, _P, _P]),
+    "sbr_set_hetero_econ_slab": (ctypes.c_int, [_P, _I32]),
     "sbr_sweep_social": (ctypes.c_int, [_P, _P, _P, _D, _P, _I64, _I64, _D, _D, _D, _P, _I32, _D, _I32, _P, _P, _P,
                                         _P]),
     "sbr_sweep_social_dev": (ctypes.c_int, [_P, _P, _P, _P, _D, _P, _I64, _I64, _D, _D, _D, _P, _I32, _D, _I32, _P,

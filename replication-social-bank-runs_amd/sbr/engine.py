@@ -605,6 +605,82 @@ class Engine:
                                           kappa, lam, ctypes.byref(opts), ctypes.byref(soa), None, None)
         check(rc, self._ctx, "sbr_sweep_hetero_dev")
 
+    # ------------------------------------------------------------------ K groups × p × λ × κ × u
+    def sweep_hetero_econ(self, betas, dist, eta, t_end, u, p, kappa, lam, x0=1e-4, knot_capacity: int = 16384,
+                          with_groups: bool = True, exhaustive: bool = False, wide: bool = False,
+                          ode_rtol: float | None = None, ode_atol: float | None = None,
+                          ode_maxiters: int | None = None, out: dict | None = None) -> dict:
+        """The heterogeneity sweep over the product of the economic axes in one call, each column
+        learned once and each (p, λ) hazard class formed once (sbr_sweep_hetero_econ).  ``betas``
+        [n_col, K], ``eta`` / ``t_end`` per column (scalars are repeated); ``u``, ``p``, ``kappa``,
+        ``lam`` are arrays or scalars, a scalar being an axis of length 1.  Returns arrays shaped
+        (n_col, n_p, n_lam, n_kappa, n_u) and, with ``with_groups``, per-group buffers (…, K); the
+        line [c, a, b, k, :] is row c of ``sweep_hetero`` at (p[a], kappa[k], lam[b]).  ``out``: the
+        caller's flat C-contiguous result arrays (xi, aw_max, tol float64; status uint32; iters
+        int32; tau_in_unc / tau_out_unc float64 with K per point when ``with_groups``)."""
+        betas = np.ascontiguousarray(np.atleast_2d(betas), np.float64)
+        n_col, K = betas.shape
+        dist = np.ascontiguousarray(dist, np.float64)
+        ax = hetero_econ_axes(n_col, eta, t_end, u, p, kappa, lam)
+        shape = (n_col, ax["p"].size, ax["lam"].size, ax["kappa"].size, ax["u"].size)
+        n = int(np.prod(shape))
+        want = {"xi": (np.float64, n), "aw_max": (np.float64, n), "tol": (np.float64, n), "status": (np.uint32, n),
+                "iters": (np.int32, n)}
+        if with_groups:
+            want.update(tau_in_unc=(np.float64, n * K), tau_out_unc=(np.float64, n * K))
+        if out is None:
+            res = {k: np.empty(sz, dt) for k, (dt, sz) in want.items()}
+        else:
+            res = {}
+            for k, (dt, sz) in want.items():
+                v = out.get(k)
+                if not isinstance(v, np.ndarray) or v.dtype != dt or v.size != sz or not v.flags["C_CONTIGUOUS"]:
+                    raise ArgumentError(f"out[{k!r}] must be a C-contiguous {np.dtype(dt).name} array of {sz}")
+                res[k] = v.reshape(-1)
+        soa = _lib.ResultSoA(_ptr(res["xi"]), None, None, _ptr(res["aw_max"]), _ptr(res["tol"]), _ptr(res["status"]),
+                             _ptr(res["iters"]))
+        opts = _opts(ode_rtol, ode_atol, ode_maxiters, knot_capacity=knot_capacity,
+                     flags=(_lib.SBR_FLAG_EXHAUSTIVE if exhaustive else 0)
+                     | (_lib.SBR_FLAG_HETERO_WIDE if wide else 0))
+        rc = self._L.sbr_sweep_hetero_econ(self._ctx, K, _ptr(betas), _ptr(dist), _ptr(ax["eta"]), _ptr(ax["t_end"]),
+                                           float(x0), _ptr(ax["u"]), n_col, shape[4], _ptr(ax["p"]), shape[1],
+                                           _ptr(ax["lam"]), shape[2], _ptr(ax["kappa"]), shape[3],
+                                           ctypes.byref(opts), ctypes.byref(soa), _ptr(res.get("tau_in_unc")),
+                                           _ptr(res.get("tau_out_unc")))
+        check(rc, self._ctx, "sbr_sweep_hetero_econ")
+        return {k: v.reshape(shape + (K,) if k.startswith("tau_") else shape) for k, v in res.items()}
+
+    def sweep_hetero_econ_dev(self, K, betas, dist, eta, t_end, u, p, kappa, lam, x0, out: dict,
+                              stream: int | None = None, knot_capacity: int = 16384, exhaustive: bool = False,
+                              wide: bool = False, flags: int = 0, ode_rtol: float | None = None,
+                              ode_atol: float | None = None, ode_maxiters: int | None = None):
+        """Device-pointer variant on torch tensors (float64 cuda; ``betas`` n_col·K, ``eta`` and
+        ``t_end`` n_col, each axis a tensor of one element or more) — enqueue only, no host sync.
+        ``out`` holds preallocated tensors xi, aw_max, tol, status (and optionally iters) with
+        n_col·n_p·n_lam·n_kappa·n_u elements, and optionally tau_in_unc / tau_out_unc with K times as
+        many.  A point whose own u, p, κ or λ breaks its rule ends as SBR_ARG_INVALID."""
+        flags |= (_lib.SBR_FLAG_HETERO_WIDE if wide else 0) | (_lib.SBR_FLAG_EXHAUSTIVE if exhaustive else 0)
+        n_col, nu, n_p, nl, nk = eta.numel(), u.numel(), p.numel(), lam.numel(), kappa.numel()
+        n = n_col * n_p * nl * nk * nu
+        xi, aw, tl, st, it = _out_ptrs(out, ("xi", "aw_max", "tol", "status", "iters"), n,
+                                       required=("xi", "aw_max", "tol", "status"))
+        tin, tout = _out_ptrs(out, ("tau_in_unc", "tau_out_unc"), n * K)
+        soa = _lib.ResultSoA(xi, None, None, aw, tl, st, it)
+        opts = _opts(ode_rtol, ode_atol, ode_maxiters, knot_capacity=knot_capacity, flags=flags)
+        rc = self._L.sbr_sweep_hetero_econ_dev(self._ctx, stream, K, _dptr(betas, "betas", _F64, n_col * K),
+                                               _dptr(dist, "dist", _F64, K), _dptr(eta, "eta", _F64),
+                                               _dptr(t_end, "t_end", _F64, n_col), x0, _dptr(u, "u", _F64), n_col, nu,
+                                               _dptr(p, "p", _F64), n_p, _dptr(lam, "lam", _F64), nl,
+                                               _dptr(kappa, "kappa", _F64), nk, ctypes.byref(opts), ctypes.byref(soa),
+                                               tin, tout)
+        check(rc, self._ctx, "sbr_sweep_hetero_econ_dev")
+
+    def set_hetero_econ_slab(self, knots: int):
+        """Knots of the LDS slab of ``sweep_hetero_econ``'s equilibrium launches (0 = the built-in
+        slab); columns with more knots run the global-memory launch, with the same results.  For
+        tests (sbr_set_hetero_econ_slab)."""
+        check(self._L.sbr_set_hetero_econ_slab(self._ctx, int(knots)), self._ctx, "sbr_set_hetero_econ_slab")
+
     def sweep_hetero_batch_dev(self, K, betas, dist, eta, t_end, u, p, kappa, lam, x0, out: dict,
                                stream: int | None = None, knot_capacity: int = 16384, flags: int = 0,
                                ode_rtol: float | None = None, ode_atol: float | None = None,
@@ -958,6 +1034,24 @@ def econ_axes(beta, eta, t_end, u, p, kappa, lam) -> dict:
             ax[name] = np.broadcast_to(np.asarray(v, np.float64), b.shape)
         except ValueError:
             raise ArgumentError(f"{name}: a scalar or one value per beta") from None
+    for name, v in (("u", u), ("p", p), ("kappa", kappa), ("lam", lam)):
+        a = np.atleast_1d(np.asarray(v, np.float64))
+        if a.ndim != 1:
+            raise ArgumentError(f"{name}: a scalar or a one-dimensional array")
+        ax[name] = a
+    return {k: np.ascontiguousarray(v) for k, v in ax.items()}
+
+
+def hetero_econ_axes(n_col: int, eta, t_end, u, p, kappa, lam) -> dict:
+    """The six arrays ``Engine.sweep_hetero_econ`` hands to sbr_sweep_hetero_econ beside betas and
+    dist: ``eta`` and ``t_end`` broadcast to the n_col columns, and each of ``u``, ``p``, ``kappa``,
+    ``lam`` a one-dimensional axis (a scalar is an axis of length 1).  Pure Python."""
+    ax = {}
+    for name, v in (("eta", eta), ("t_end", t_end)):
+        try:
+            ax[name] = np.broadcast_to(np.asarray(v, np.float64), (n_col,))
+        except ValueError:
+            raise ArgumentError(f"{name}: a scalar or one value per column") from None
     for name, v in (("u", u), ("p", p), ("kappa", kappa), ("lam", lam)):
         a = np.atleast_1d(np.asarray(v, np.float64))
         if a.ndim != 1:
