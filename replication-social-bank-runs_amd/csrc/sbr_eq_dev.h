@@ -97,7 +97,14 @@ __device__ __forceinline__ void solve_from_buffers(P T, P G, P H, const Summ& S,
     const bool okmin = in_range(xmin, tlo, thi, trunc, flag);
     const bool okmax = in_range(xmax, tlo, thi, trunc, flag);
     if (!okmin || !okmax) {
-        r.status = flag | lbits;
+        // a buffer outside the grid (NaN from a NaN or zero-width hazard bracket): the BoundsError of the
+        // reference's first iteration, after that iteration's collapse and iteration-cap tests
+        if (max_iters >= 1) {
+            r.iters = 1;
+            r.status = (collapsed(xmin - xmax) ? SBR_NO_RUN_COLLAPSE : max_iters == 2 ? SBR_NO_RUN_MAXITER : flag) | lbits;
+        } else {
+            r.status = SBR_NO_RUN_MAXITER | lbits;
+        }
         return;
     }
     int jlo = ssl_range(T, 0, n - 1, xmin);
@@ -141,7 +148,9 @@ __device__ __forceinline__ void solve_from_buffers(P T, P G, P H, const Summ& S,
             if (collapsed(dd)) { s = SBR_NO_RUN_COLLAPSE; break; }
             if (iter == max_iters - 1) { s = SBR_NO_RUN_MAXITER; break; }
             const double xo = xnew;
-            const int j = ssl_range(T, jlo, jhi, xo); // t[jlo] <= ξmin <= xo <= ξmax < t[jhi+1]
+            // t[jlo] <= ξmin <= xo <= ξmax < t[jhi+1]; on a grid that is not moderate a midpoint may overflow
+            // past ξmax, and the reference's search is over the whole grid (±Inf and NaN end in its BoundsError)
+            const int j = (ORD || moderate) ? ssl_range(T, jlo, jhi, xo) : ssl_range(T, 0, n - 1, xo);
             double ic, oc, Goc, Gic = 0.0;
             int joc, jic = 0;
             if constexpr (ORD) {

@@ -116,7 +116,17 @@ __device__ __forceinline__ void point_wave(P T, P G, P H, const int n, const int
     double xnew = (tin + tout) / 2.0, xmin = tin, xmax = tout;
     const bool okmin = co_in_range(xmin, tlo, thi, trunc, flag);
     const bool okmax = co_in_range(xmax, tlo, thi, trunc, flag);
-    if (!okmin || !okmax) { r.status = flag | lbits; return; }
+    if (!okmin || !okmax) { // the BoundsError of the reference's first iteration (solve_from_buffers)
+        if (max_iters >= 1) {
+            r.iters = 1;
+            r.status = (collapsed(xmin - xmax) ? SBR_NO_RUN_COLLAPSE : max_iters == 2 ? SBR_NO_RUN_MAXITER : flag) | lbits;
+        } else {
+            r.status = SBR_NO_RUN_MAXITER | lbits;
+        }
+        return;
+    }
+    // brackets [jlo, jhi] hold the iterates of a moderate grid; elsewhere a midpoint may overflow past ξmax
+    const bool moderate = tlo >= -0x1p1000 && thi <= 0x1p1000;
     int jlo = wave_ssl(T, 0, n - 1, xmin);
     int jhi = wave_ssl(T, 0, n - 1, xmax);
     const int jtin = jlo;
@@ -147,7 +157,7 @@ __device__ __forceinline__ void point_wave(P T, P G, P H, const int n, const int
             else if (it == max_iters - 1) term = 2;
             else {
                 ic = dmin(tin, xo); oc = dmin(tout, xo);
-                j = ssl_range(T, jlo, jhi, xo);
+                j = moderate ? ssl_range(T, jlo, jhi, xo) : ssl_range(T, 0, n - 1, xo);
                 const bool ok = co_in_range(oc, tlo, thi, trunc, nflag);
                 joc = (oc == xo) ? j : (ok ? ssl_range(T, 0, n - 1, oc) : 0);
                 const double Goc = ok ? lerp_at(T, G, n, joc, oc) : 0.0;

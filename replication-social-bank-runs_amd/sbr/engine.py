@@ -445,7 +445,7 @@ class Engine:
 
     def equilibrium_on_knots(self, t, G, beta, eta, t_end, u, p, kappa, lam, max_iters: int = 100,
                              paths: bool = True, exhaustive: bool = False, xi_guess: float | None = None,
-                             pdf=None) -> dict:
+                             pdf=None, flags: int = 0) -> dict:
         """solve_equilibrium_baseline(lr, econ) + get_AW_functions!(r) (solver.jl:413-462, 553-576)
         on the learning knots the caller holds (t, G = lr.learning_cdf's knots and values) for each
         u — no learning ODE (sbr_equilibrium_on_knots).  The knots and the hazard path stay on the
@@ -454,7 +454,8 @@ class Engine:
         ``tau``, ``hr`` and ``aw_cum`` / ``aw_out`` / ``aw_in`` on it (NaN without a run).
         ``xi_guess``: compute_ξ's first iterate (solver.jl:413,441; None = the midpoint).
         ``pdf``: the learning pdf's values on the knots (sbr_equilibrium_on_knots_pdf; ``beta`` is
-        then unused) — the social extension's (1 − G)·β·AW_{n−1}; None = βG(1 − G)."""
+        then unused) — the social extension's (1 − G)·β·AW_{n−1}; None = βG(1 − G).
+        ``flags``: further SBR_FLAG_* bits for the call's options (the SBR_FLAG_DIAG_* counters)."""
         t = t if (isinstance(t, np.ndarray) and t.dtype == np.float64 and t.flags.c_contiguous) else \
             np.ascontiguousarray(t, np.float64)
         G = G if (isinstance(G, np.ndarray) and G.dtype == np.float64 and G.flags.c_contiguous) else \
@@ -470,7 +471,7 @@ class Engine:
         base = res.ctypes.data
         soa = _lib.ResultSoA(base, base + 8 * nu, base + 16 * nu, base + 24 * nu, base + 32 * nu, base + 40 * nu,
                              base + 44 * nu)
-        key = (max_iters, exhaustive, xi_guess)
+        key = (max_iters, exhaustive, xi_guess, flags)
         opts = self._knot_opts.get(key)
         if opts is None:
             if len(self._knot_opts) > 64:  # per-call guesses: keep the cache bounded
@@ -478,7 +479,7 @@ class Engine:
             opts = self._knot_opts[key] = _lib.default_opts(
                 bisect_max_iters=max_iters,
                 flags=(_lib.SBR_FLAG_EXHAUSTIVE if exhaustive else 0)
-                | (_lib.SBR_FLAG_XI_GUESS if xi_guess is not None else 0),
+                | (_lib.SBR_FLAG_XI_GUESS if xi_guess is not None else 0) | flags,
                 xi_guess=float("nan") if xi_guess is None else float(xi_guess))
         cap = n + 1
         nt = ctypes.c_int64()
